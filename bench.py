@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the DAS4Whales hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 20000] [--ns 120000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 20000] [--ns 120000] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one [nx x ns] float32 strain block that is already
 resident in HBM: the f-k filter (dsp.fk_filter_filt) followed by the HF+LF fin-whale matched filter
@@ -15,8 +15,14 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): every rank filters 
 in the data path, weak scaling; the timed region is bracketed by barrier + synchronize and the
 MAX over ranks is reported.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-live HIP-event timing) and `cpu_baseline` (NumPy oracle on a bounded sample, rank 0, N = 1 only).
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of one timed step).
+A plain run sets up, warms up, times the K steps and prints that line.  --full adds, after the timed steps, everything
+else the line used to carry: the other API composition, `roofline` (dominant kernel, per-kernel HIP-event timing, the
+other masks, the band-pass) and `cpu_baseline` (NumPy oracle on a bounded sample, rank 0, N = 1 only).
+
+--dump-outputs DIR writes what the last timed step returned (the HF and LF correlograms of the default stages) as
+DIR/<name>.npy; outputs too large for the 64-MB budget are sampled the same way in every run (dump_outputs below).
+The input block comes from a seeded generator, so the same arguments give the same inputs from run to run.
 """
 import argparse
 import json
@@ -39,6 +45,42 @@ PASS_NAMES_TF = ["fk_passA_fwd", "fk_passBf_time_fwd", "fk_passCm_channel", "fk_
 # operands on the matrix cores and accumulates in float32 (22-23 significant bits per operand)
 DTYPE = "f32 (matched filter: 2 x f16 split operands on the matrix cores, f32 accumulate)"
 
+DUMP_BUDGET = 64 * 2 ** 20     # bytes, all files --dump-outputs writes together
+DUMP_SEED = 20240              # the sample of a large output is drawn with this seed, the same in every run
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: write `outs` ({name: tensor}, what the timed step returned) as <path>/<name>.npy, float32 (float64
+    when the output is float64).  An output larger than its share of DUMP_BUDGET is sampled instead, with DUMP_SEED:
+    whole rows (<name>_rows.npy, their indices in <name>_row_index.npy) and single elements spread over the whole array
+    (<name>_points.npy, flat indices in <name>_point_index.npy); indices are stored as float64 (exact below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BUDGET - 2 ** 20) // max(1, len(outs))
+    written = {}
+    for name, t in outs.items():
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        esz = 8 if dt == torch.float64 else 4
+        t2 = t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(1, -1)
+        nrow, ncol = t2.shape
+        files = {}
+        if t.numel() * esz <= share:
+            files[name] = t.to(dt).cpu().numpy()
+        else:
+            rng = np.random.default_rng(DUMP_SEED)
+            r = int(min(nrow, 32, (share // 2) // (ncol * esz + 8)))
+            rows = np.sort(rng.choice(nrow, r, replace=False))
+            k = int(min(t.numel(), 1 << 20, (share // 2) // (esz + 8)))
+            pts = np.sort(rng.choice(t.numel(), k, replace=False))
+            if r:
+                files[name + "_rows"] = t2.index_select(0, torch.from_numpy(rows).to(t.device)).to(dt).cpu().numpy()
+                files[name + "_row_index"] = rows.astype(np.float64)
+            files[name + "_points"] = t.reshape(-1)[torch.from_numpy(pts).to(t.device)].to(dt).cpu().numpy()
+            files[name + "_point_index"] = pts.astype(np.float64)
+        for fn, a in files.items():
+            np.save(os.path.join(path, fn + ".npy"), a)
+            written[fn] = list(a.shape)
+    return written
 
 
 def _best_of(fn, n=3):
@@ -717,9 +759,17 @@ def main():
                          "(shard.all_gather_rows(how='direct')); the other form is timed beside the step and both are printed")
     ap.add_argument("--no-replicas", action="store_true", help="N > 1: skip the second (replicas, weak-scaling) measurement")
     ap.add_argument("--force-replicas", action="store_true", help="run the second measurement at N = 1 as well (exercises the N > 1 code path)")
+    ap.add_argument("--full", action="store_true",
+                    help="block step: after the timed steps, also time the other API composition, the per-kernel roofline (other "
+                         "masks, band-pass) and the CPU baseline; a plain run only sets up, warms up, times the steps and prints")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="block step: write what the last timed step returned to DIR/<name>.npy (float32; large outputs as a "
+                         "fixed seeded sample, 64 MB in all)")
     args = ap.parse_args()
     stages = [t for t in args.stages.split(",") if t]
     assert set(stages) <= {"bp", "fk", "mf"} and stages, "--stages: comma list of bp, fk, mf"
+    if args.dump_outputs and (args.backend == "gloo" or args.config != "block"):
+        ap.error("--dump-outputs: only the single-device block step writes its outputs")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU under
@@ -741,6 +791,8 @@ def main():
         sys.exit(2)
     if args.shard == "auto":
         args.shard = "channel" if world > 1 else "replicas"
+    if args.dump_outputs and args.shard == "channel":
+        ap.error("--dump-outputs: only the single-device block step writes its outputs (add --shard replicas)")
     if args.gather is None:
         # BASELINE configs[3] / north star: "a single RCCL all-gather over xGMI to reassemble the filtered t-x matrix" is part
         # of the sharded step; the step with its outputs left sharded is timed beside it (outputs_sharded)
@@ -851,8 +903,12 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    last = None
+    for i in range(args.steps):
+        if i + 1 < args.steps:
+            step()
+        else:
+            last = step()                                # what the caller of the timed path receives (--dump-outputs)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -865,7 +921,41 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     samples = float(nx) * ns
     value = samples * world / (dt / args.steps)
-    # the other composition on the same box, right behind the timed region (not part of `value`)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        outs = list(last) if isinstance(last, (list, tuple)) else [last]
+        names = ["corr_hf", "corr_lf"] if ("mf" in stages and len(outs) == 2) else \
+            ["corr_%d" % i for i in range(len(outs))] if "mf" in stages else ["filtered"]
+        dumped = dump_outputs(args.dump_outputs, dict(zip(names, outs)))
+    last = None
+
+    def headline():
+        out = {"metric": "channel-samples/sec through " + " + ".join(
+                   {"bp": "band-pass", "fk": "f-k filter", "mf": "matched-filter"}[t] for t in stages), "value": value,
+               "unit": "channel-samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
+               "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
+               "config": {"workload": "%d channels x %d samples float32 per GPU, classic f-k fan mask "
+                                      "(fk_filter_design defaults), stages %s, HF+LF fin-call templates"
+                                      % (nx, ns, "+".join(stages)),
+                          "api": args.api,
+                          "api_note": ("the timed step is the public calls dsp.fk_filter_filt(x, mask) + detect.compute_cross_correlograms(y, "
+                                       "[hf, lf]) on full-length zero-padded templates (DC tail of detect.py:158 included)"
+                                       if args.api == "public" else
+                                       "the timed step is FkPlan.apply_stats + detect._xcorr_device on support-only templates (rounds 1-5)"),
+                          "plan": plan.info(), "parallelism": "independent channel blocks x%d" % world}}
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        return out
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # --full: the other composition on the same box, right behind the timed region (not part of `value`)
     ms_other = None
     if opts is None:
         try:
@@ -1034,22 +1124,9 @@ def main():
                               "frac": 8.0 * samples / (tb * 1e-3) / 1e9 / HBM_PEAK_GBS}
 
     if rank == 0:
-        out = {"metric": "channel-samples/sec through " + " + ".join(
-                   {"bp": "band-pass", "fk": "f-k filter", "mf": "matched-filter"}[t] for t in stages), "value": value,
-               "unit": "channel-samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
-               "config": {"workload": "%d channels x %d samples float32 per GPU, classic f-k fan mask "
-                                      "(fk_filter_design defaults), stages %s, HF+LF fin-call templates"
-                                      % (nx, ns, "+".join(stages)),
-                          "api": args.api,
-                          "api_note": ("the timed step is the public calls dsp.fk_filter_filt(x, mask) + detect.compute_cross_correlograms(y, "
-                                       "[hf, lf]) on full-length zero-padded templates (DC tail of detect.py:158 included)"
-                                       if args.api == "public" else
-                                       "the timed step is FkPlan.apply_stats + detect._xcorr_device on support-only templates (rounds 1-5)"),
-                          ("ms_per_step_private_composition" if args.api == "public" else "ms_per_step_public_calls"): ms_other,
-                          "plan": plan.info(), "parallelism": "independent channel blocks x%d" % world},
-               "roofline": roofline}
+        out = headline()
+        out["config"]["ms_per_step_private_composition" if args.api == "public" else "ms_per_step_public_calls"] = ms_other
+        out["roofline"] = roofline
         if world == 1 and not args.no_cpu:
             snx, sns = [int(v) for v in args.cpu_sample.split("x")]
             out["cpu_baseline"] = cpu_baseline(snx, sns, stages)

@@ -16,6 +16,6 @@ cp das4whales_amd/lib/libd4w.so das4whales_amd/lib/libd4w_keep.so
 for tag in "$@"; do
   cp das4whales_amd/lib/libd4w_$tag.so das4whales_amd/lib/libd4w.so
   echo "--- $tag ${ENVS:-} ${BENCH_ARGS:-}"
-  env ${ENVS:-A=1} python bench.py --steps 5 --warmup 2 --no-cpu ${BENCH_ARGS:-} 2>&1 | python -c "$fmt"
+  env ${ENVS:-A=1} python bench.py --full --steps 5 --warmup 2 --no-cpu ${BENCH_ARGS:-} 2>&1 | python -c "$fmt"
 done
 cp das4whales_amd/lib/libd4w_keep.so das4whales_amd/lib/libd4w.so

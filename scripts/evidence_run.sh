@@ -10,10 +10,10 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 timeout 1500 python -m pytest tests -q -m gpu -s > $O/pytest_gpu.log 2>&1; grep -E "passed|failed" $O/pytest_gpu.log | tail -2
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; grep "smoke" $O/smoke.log
-timeout 900 python bench.py --steps 20 --warmup 5 2>/dev/null | grep "^{" > $O/bench_line.json; cut -c1-300 $O/bench_line.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>/dev/null | grep "^{" > $O/bench_line.json; cut -c1-300 $O/bench_line.json
 # round 6: the default line times the PUBLIC calls; the composition of rounds 1-5 (plan.apply_stats + _xcorr_device, no tail term) beside it
-timeout 900 python bench.py --steps 20 --warmup 5 --api private --no-cpu --no-dense 2>/dev/null | grep "^{" > $O/bench_line_private_api.json; cut -c1-200 $O/bench_line_private_api.json
-timeout 900 python bench.py --stages bp,fk,mf --steps 10 --warmup 3 --no-cpu --no-dense 2>/dev/null | grep "^{" > $O/bench_bp_fk_mf.json; cut -c1-200 $O/bench_bp_fk_mf.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 --api private --no-cpu --no-dense 2>/dev/null | grep "^{" > $O/bench_line_private_api.json; cut -c1-200 $O/bench_line_private_api.json
+timeout 900 python bench.py --full --stages bp,fk,mf --steps 10 --warmup 3 --no-cpu --no-dense 2>/dev/null | grep "^{" > $O/bench_bp_fk_mf.json; cut -c1-200 $O/bench_bp_fk_mf.json
 timeout 900 python bench.py --config stream --steps 10 --warmup 2 2>/dev/null | grep "^{" > $O/bench_stream_1gpu.json; cut -c1-600 $O/bench_stream_1gpu.json
 # ... with the two detectors of a file on a side stream each (the default of round 5; since round 6 everything runs on one stream)
 timeout 900 python bench.py --config stream --steps 10 --warmup 2 --detector-streams 2 --no-cpu 2>/dev/null | grep "^{" > $O/bench_stream_1gpu_detector_side_streams.json; cut -c1-300 $O/bench_stream_1gpu_detector_side_streams.json
@@ -51,11 +51,11 @@ timeout 500 python scripts/probe/time_bz_band.py 2>/dev/null | grep "^{" > $O/ti
 timeout 250 python scripts/time_fk_filt.py 2>/dev/null | grep "^{" > $O/time_fk_filt.txt
 (timeout 300 python scripts/time_api_sweep.py; NX=11020 NS=12000 timeout 300 python scripts/time_api_sweep.py) 2>/dev/null | grep "^{" > $O/time_api_sweep.txt
 NX=11020 timeout 600 python scripts/time_spectral.py 2>/dev/null | grep "^{" > $O/time_spectral_11020x12000.json
-cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o fk -- python $R/bench.py --steps 5 --warmup 2 --no-cpu > $R/$O/rocprof_bench.log 2>&1
+cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o fk -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu > $R/$O/rocprof_bench.log 2>&1
 cd $R
 f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/kernel_stats.csv && grep -E "d4w|Name" "$f" | cut -c1-160 | head -16
 rm -rf $O/prof
-cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o fk -- python $R/bench.py --stages bp,fk,mf --steps 5 --warmup 2 --no-cpu --no-dense > $R/$O/rocprof_bench_bp.log 2>&1
+cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o fk -- python $R/bench.py --full --stages bp,fk,mf --steps 5 --warmup 2 --no-cpu --no-dense > $R/$O/rocprof_bench_bp.log 2>&1
 cd $R
 f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/kernel_stats_bp_fk_mf.csv
 rm -rf $O/prof

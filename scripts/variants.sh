@@ -10,5 +10,5 @@ for l in sys.stdin:
 '
 for e in "$@"; do
   echo "--- $e"
-  env $e python bench.py --steps 5 --warmup 2 --no-cpu --stages fk 2>&1 | python -c "$fmt"
+  env $e python bench.py --full --steps 5 --warmup 2 --no-cpu --stages fk 2>&1 | python -c "$fmt"
 done

@@ -32,8 +32,5 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
-
-    def load(name):
-        return np.load(os.path.join(GOLDEN, name))
+    from tests.golden_npz import load        # tests/golden/<name>, or its pieces of < 1 MiB each
     return load

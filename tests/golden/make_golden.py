@@ -2,7 +2,8 @@
 
 Run in the build container only (needs /root/reference):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py                  # every fixture
+    python tests/golden/make_golden.py --signatures     # reference_signatures.json only
 
 It imports leabouffaut/DAS4Whales from /root/reference/src under oracle/ref_harness.py (stubs
 for the absent I/O / plotting deps, a functional sparse.COO shim, and the librosa.stft
@@ -21,6 +22,7 @@ sys.path.insert(0, ROOT)
 
 from oracle.ref_harness import import_reference  # noqa: E402
 from oracle import d4w_oracle as orc  # noqa: E402
+from tests.golden_npz import save  # noqa: E402   (fixtures above 1 MiB are written in pieces)
 
 FS = 200.0
 DX = 2.0419046878814697
@@ -70,7 +72,7 @@ def main():
     out["snr_env"] = dw.dsp.snr_tr_array(x, env=True)
     out["fx"] = dw.dsp.get_fx(x[:, :400], 512)
     out["ifreq"] = dw.dsp.instant_freq(x[3], FS)
-    np.savez_compressed(os.path.join(HERE, "fk_40x480.npz"), **out)
+    save(os.path.join(HERE, "fk_40x480.npz"), out)
 
     # ------------------------------------------------------------------ odd-ish shape: 30 x 360 (nx not /4)
     nx2, ns2 = 30, 360
@@ -160,7 +162,7 @@ def main():
     assert np.array_equal(dw.improcess.apply_smooth_mask(trf64, img["mask_sparse"]), trf64 * img["mask_sparse"])
     img["scale_pixels"] = dw.improcess.scale_pixels(trf64[:4])
     img["image"] = img["image"].astype(np.float32)                            # fixture size; 6e-8 relative
-    np.savez_compressed(os.path.join(HERE, "image_240x1600.npz"), **img)
+    save(os.path.join(HERE, "image_240x1600.npz"), img)
 
     # ------------------------------------------------------------------ reference's own pinned vectors
     # tests/test_dsp.py:85-88 (taper) and :136-141 (snr) -- literal values from the reference tests.
@@ -171,10 +173,29 @@ def main():
                         snr_in=lit,
                         snr_expected=np.array([[-3.01029996, 3.01029996, 6.53212514, 9.03089987, 10.96910013]] * 2),
                         snr_out=dw.dsp.snr_tr_array(lit.copy()))
+    signatures(dw)
     for fn in sorted(os.listdir(HERE)):
-        if fn.endswith(".npz"):
+        if fn.endswith((".npz", ".json")):
             print(fn, os.path.getsize(os.path.join(HERE, fn)) // 1024, "KiB")
 
 
+def signatures(dw=None):
+    """reference_signatures.json: name, parameter names and defaults of every function the reference's dsp / detect /
+    improcess modules define (what tests/test_signatures.py holds the Python mirror to)."""
+    import inspect
+    import json
+    dw = dw or import_reference()
+    out = {}
+    for mod in ("dsp", "detect", "improcess"):
+        rm = getattr(dw, mod)
+        out[mod] = {name: [[p.name, "<required>" if p.default is inspect.Parameter.empty else p.default]
+                           for p in inspect.signature(fn).parameters.values()]
+                    for name, fn in inspect.getmembers(rm, inspect.isfunction) if fn.__module__ == rm.__name__}
+    with open(os.path.join(HERE, "reference_signatures.json"), "w") as f:         # one line per function
+        f.write("{\n" + ",\n".join(
+            " %s: {\n" % json.dumps(mod) + ",\n".join("  %s: %s" % (json.dumps(n), json.dumps(ps)) for n, ps in sorted(fns.items()))
+            + "\n }" for mod, fns in sorted(out.items())) + "\n}\n")
+
+
 if __name__ == "__main__":
-    main()
+    signatures() if "--signatures" in sys.argv else main()

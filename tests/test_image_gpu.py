@@ -1,16 +1,15 @@
 """GPU parity of the Gabor image pipeline against the
 fixture generated from the reference's improcess code and against the oracle on larger blocks."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import d4w_oracle as orc
+from tests import golden_npz
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "image_240x1600.npz"))
+G = golden_npz.load("image_240x1600.npz")
 
 
 def rel(y, ref):

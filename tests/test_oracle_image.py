@@ -1,15 +1,14 @@
 """Oracle of the Gabor image pipeline against the fixture generated from the
 reference's own improcess functions (tests/golden/make_golden.py) and against torch's CPU kernel for
 the antialiased bilinear resize (the arithmetic torchvision 0.17 Resize delegates to)."""
-import os
-
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from oracle import d4w_oracle as orc
+from tests import golden_npz
 
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "image_240x1600.npz"))
+G = golden_npz.load("image_240x1600.npz")
 
 
 def close(a, b, tol=1e-11):

@@ -134,6 +134,7 @@ def _fk_worker(rank, world, port, q):
     try:
         import ctypes
         import numpy as np
+        from tests import golden_npz
         from tests.emu_util import load_emu
         emu = load_emu()
         for name in ("d4w_fkd_plan_create", "d4w_fkd_plan_info", "d4w_fkd_plan_q1_owner", "d4w_fkd_set_mask_dense_f32",
@@ -151,7 +152,7 @@ def _fk_worker(rank, world, port, q):
         def check(rc):
             assert rc == 0, emu.d4w_last_error()
         shard = _load_shard()
-        g = np.load(os.path.join(ROOT, "tests", "golden", "fk_40x480.npz"))
+        g = golden_npz.load("fk_40x480.npz")
         x = torch.from_numpy(g["x"]).float()
         nx = x.shape[0]
         a, b = shard.channel_block(nx, world, rank)
