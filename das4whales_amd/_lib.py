@@ -152,6 +152,9 @@ def _load():
         "d4w_filter2d_mm_eligible": (c_int, [c_int, c_int]),
         "d4w_filter2d_mm_ws_bytes": (ctypes.c_size_t, [c_int, c_int]),
         "d4w_filter2d_mm_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+        "d4w_radon_size": (c_int, [c_int, c_int]),
+        "d4w_radon_ws_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
+        "d4w_radon_f32": (c_int, [c_void_p, c_int, c_int, P(ctypes.c_double), c_int, c_void_p, c_void_p, c_void_p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch: fail loudly

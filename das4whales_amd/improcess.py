@@ -11,11 +11,16 @@ reference's `das4whales.improcess` that scripts/main_gabordetect.py:78-166 runs,
 `gabor_mask` runs those steps in one call with everything resident on the device.  cv2 and torchvision
 are not used (and not installed): `gabor_filt_design` evaluates OpenCV's getGaborKernel formula on the
 host in float64, `filter2d` and `binning` are HIP kernels (csrc/image.hip) that follow cv2.filter2D
-(correlation, BORDER_REFLECT_101) and aten's antialiased bilinear interpolation.  The functions of
-improcess.py that the detector does not use (Canny / Hough / Radon / bilateral experiments) are out
-of scope.  Arrays: NumPy in -> NumPy out (float dtype kept, compute in float32), CUDA tensor in ->
-CUDA tensor out; masks are bool.
+(correlation, BORDER_REFLECT_101) and aten's antialiased bilinear interpolation.
+
+`compute_radon_transform` (improcess.py:347-367) is skimage.transform.radon(image, theta, circle=False)
+as a HIP kernel (csrc/radon.hip).  The other functions of improcess.py that the detector does not use
+(Canny / Hough / bilateral / Gaussian experiments, the edge stencils) are out of scope.  Arrays: NumPy
+in -> NumPy out (float dtype kept, compute in float32), CUDA tensor in -> CUDA tensor out; masks are
+bool.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -207,3 +212,68 @@ def gabor_mask(trf_fk, fs, dx, selected_channels, c0=1500., threshold=9100., thr
     for k, v in res.items():
         out[k] = v.cpu().numpy() if v.dtype == torch.bool else dev.like_input(v, trf_fk)
     return out
+
+
+def _radon_input(image):
+    """skimage's convert_to_float(image, preserve_range=False): float32 / float64 kept, other floats computed in float32,
+    bool as 0 / 1, unsigned integers / max, signed integers (2 x + 1) / (max - min) (img_as_float).  Returns the float32
+    CUDA tensor and the NumPy dtype of the result (None for tensors)."""
+    if dev.is_tensor(image):
+        x = image
+        if x.dtype == torch.bool:
+            x = x.to(torch.float32)
+        elif not x.dtype.is_floating_point:
+            if x.dtype.is_complex:
+                raise TypeError("compute_radon_transform: complex images are not supported")
+            info = torch.iinfo(x.dtype)
+            x = x.to(torch.float64)
+            x = x / float(info.max) if info.min == 0 else (2.0 * x + 1.0) / float(info.max - info.min)
+        return dev.to_device_f32(x), None
+    a = np.asarray(image)
+    if a.dtype.kind == "f":
+        return dev.upload_f32(a), a.dtype
+    if a.dtype.kind == "b":
+        return dev.upload_f32(a), np.dtype(np.float64)
+    if a.dtype.kind == "u":
+        return dev.upload_f32(a / float(np.iinfo(a.dtype).max)), np.dtype(np.float64)
+    if a.dtype.kind == "i":
+        info = np.iinfo(a.dtype)
+        return dev.upload_f32((2.0 * a.astype(np.float64) + 1.0) / float(info.max - info.min)), np.dtype(np.float64)
+    raise TypeError("compute_radon_transform: unsupported image dtype %s" % a.dtype)
+
+
+def _radon_device(x, theta):
+    """Sinogram [P, len(theta)] of the float32 CUDA image x; theta = float64 NumPy angles in degrees."""
+    h, w = x.shape
+    n = int(theta.size)
+    P = lib.d4w_radon_size(h, w)
+    if P < 0:
+        check(P)
+    out = torch.empty((P, n), dtype=torch.float32, device=x.device)
+    if n == 0:
+        return out
+    with torch.cuda.device(x.device):
+        ws = torch.empty(int(lib.d4w_radon_ws_bytes(h, w, n)), dtype=torch.uint8, device=x.device)
+        check(lib.d4w_radon_f32(dev.ptr(x), h, w, theta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n,
+                                dev.out_ptr(out), dev.ptr(ws), dev.stream_ptr(x)))
+    return out
+
+
+def compute_radon_transform(image, theta=None):
+    """Radon transform of a 2-D image -- reference improcess.py:347-367, skimage.transform.radon(image, theta,
+    circle=False): the image zero-padded to P x P (P = ceil(sqrt(2) max(h, w)), centred as skimage pads it), each angle
+    (degrees, default np.arange(180)) a bilinear rotation about P // 2 summed over rows.  Returns [P, len(theta)]: NumPy
+    in the dtype skimage returns (float32 / float64 kept, integers and bool as float64), a CUDA tensor as float32."""
+    if getattr(image, "ndim", np.ndim(image)) != 2:
+        raise ValueError("The input image must be 2-D")
+    th = np.arange(180, dtype=np.float64) if theta is None else theta
+    if dev.is_tensor(th):
+        th = th.detach().cpu().numpy()
+    th = np.ascontiguousarray(th, dtype=np.float64)
+    if th.ndim != 1:
+        raise ValueError("theta must be a 1-D array of angles in degrees")
+    x, dtype = _radon_input(image)
+    y = _radon_device(x, th)
+    if dev.is_tensor(image):
+        return y if image.is_cuda else y.to(image.device)
+    return dev.download(y, dtype)

@@ -565,6 +565,23 @@ size_t d4w_filter2d_mm_ws_bytes(int kh, int kw);
 int d4w_filter2d_mm_f32(const float* img, int h, int w, const float* kernel, int kh, int kw, float* out,
                         int accumulate, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Radon transform: replaces improcess.compute_radon_transform (improcess.py:347-367), i.e.
+ * skimage.transform.radon(image, theta, circle=False) (das4whales_amd/csrc/radon.hip).
+ *
+ * d4w_radon_size: P = ceil(sqrt(2) max(h, w)), the side of the zero-padded square and the number of
+ *   sinogram rows; -1 for an empty image.
+ * d4w_radon_f32: out[c][i] = sum_r bilinear(img padded to P x P, y, x) with, for a = theta_deg[i] in radians and
+ *   c0 = P / 2, x = cos a c + sin a r - c0 (cos a + sin a - 1), y = -sin a c + cos a r - c0 (cos a - sin a - 1);
+ *   pad_before = P / 2 - {h, w} / 2, zeros outside the image.  img = DEVICE [h][w], out = DEVICE [P][ntheta],
+ *   theta_deg = HOST [ntheta] degrees (finite, any range); ntheta = 0 writes nothing.  ws = DEVICE scratch of
+ *   d4w_radon_ws_bytes(h, w, ntheta) bytes (the per-angle cos / sin table).  Run-to-run bit-identical.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_radon_size(int h, int w);
+size_t d4w_radon_ws_bytes(int h, int w, int ntheta);
+int d4w_radon_f32(const float* img, int h, int w, const double* theta_deg_host, int ntheta, float* out, void* ws,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
