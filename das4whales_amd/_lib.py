@@ -155,6 +155,14 @@ def _load():
         "d4w_radon_size": (c_int, [c_int, c_int]),
         "d4w_radon_ws_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
         "d4w_radon_f32": (c_int, [c_void_p, c_int, c_int, P(ctypes.c_double), c_int, c_void_p, c_void_p, c_void_p]),
+        "d4w_stencil_zero_f32": (c_int, [c_void_p, c_int, c_int, P(ctypes.c_double), c_int, c_int, c_int, c_int, c_void_p,
+                                         c_void_p]),
+        "d4w_gradient_oriented_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+        "d4w_gaussian_blur_ws_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+        "d4w_gaussian_blur_f32": (c_int, [c_void_p, c_int, c_int, P(ctypes.c_double), P(ctypes.c_double), c_int, c_int, c_void_p,
+                                          c_void_p, c_void_p]),
+        "d4w_bilateral_max_tiled_radius": (c_int, []),
+        "d4w_bilateral_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch: fail loudly

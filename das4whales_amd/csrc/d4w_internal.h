@@ -128,13 +128,15 @@ __device__ __forceinline__ void st_stream(float2* p, float2 v) {
 #endif
 }
 
-// 24-bit integer multiply (full-rate v_mul_i32_i24; v_mul_lo_u32 is quarter rate) and fast reciprocal
+// 24-bit integer multiply (full-rate v_mul_i32_i24; v_mul_lo_u32 is quarter rate), fast reciprocal and fast exp
 #ifdef D4W_EMU
 __device__ __forceinline__ int d4w_mul24(int a, int b) { return a * b; }
 __device__ __forceinline__ float d4w_rcp(float x) { return 1.0f / x; }
+__device__ __forceinline__ float d4w_expf(float x) { return expf(x); }
 #else
 __device__ __forceinline__ int d4w_mul24(int a, int b) { return __mul24(a, b); }
 __device__ __forceinline__ float d4w_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float d4w_expf(float x) { return __expf(x); }      // v_exp_f32 of x log2(e)
 #endif
 
 // Cache policy of the f-k passes' streaming accesses to the block (round 6).  A 9.6-GB block is read once and written once per

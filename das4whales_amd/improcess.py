@@ -14,12 +14,25 @@ host in float64, `filter2d` and `binning` are HIP kernels (csrc/image.hip) that 
 (correlation, BORDER_REFLECT_101) and aten's antialiased bilinear interpolation.
 
 `compute_radon_transform` (improcess.py:347-367) is skimage.transform.radon(image, theta, circle=False)
-as a HIP kernel (csrc/radon.hip).  The other functions of improcess.py that the detector does not use
-(Canny / Hough / bilateral / Gaussian experiments, the edge stencils) are out of scope.  Arrays: NumPy
+as a HIP kernel (csrc/radon.hip).
+
+The image operators outside the detector are HIP kernels too (csrc/edges.hip):
+
+    gradient_oriented(image, direction)          improcess.py:143-169   recorded from the reference
+    detect_diagonal_edges(matrix, threshold)     improcess.py:172-226   recorded from the reference
+    diagonal_edge_detection(img, threshold)      improcess.py:229-266   recorded from the reference
+    gaussian_filter(img, size, sigma)            improcess.py:370-392   documented definition, unpinned
+    bilateral_filter(img, diameter, sigma_color, sigma_space)   :319-344   documented definition, unpinned
+
+The first three are tested against outputs recorded from the reference itself (tests/golden/edges.npz).  The last
+two are cv2.GaussianBlur and cv2.bilateralFilter; cv2 is not installed, so they follow OpenCV's documented
+definitions (tests/known_answers_smooth.py) and their agreement with a real cv2 is not measured.  Only
+`detect_long_lines` (Canny + randomised probabilistic Hough + plt.show()) is out of scope.  Arrays: NumPy
 in -> NumPy out (float dtype kept, compute in float32), CUDA tensor in -> CUDA tensor out; masks are
 bool.
 """
 import ctypes
+import operator
 
 import numpy as np
 import torch
@@ -277,3 +290,178 @@ def compute_radon_transform(image, theta=None):
     if dev.is_tensor(image):
         return y if image.is_cuda else y.to(image.device)
     return dev.download(y, dtype)
+
+
+_P_DOUBLE = ctypes.POINTER(ctypes.c_double)
+
+
+def _require_2d(a, name):
+    if getattr(a, "ndim", np.ndim(a)) != 2:
+        raise ValueError("%s must be a 2-D array" % name)
+
+
+def _stencil_device(x, kernel, anchor):
+    """Correlation of the float32 CUDA image x with a float64 host kernel of at most 7 x 7, zeros outside the image."""
+    h, w = x.shape
+    k = np.ascontiguousarray(kernel, dtype=np.float64)
+    out = torch.empty_like(x)
+    if _n(x) == 0:
+        return out
+    with torch.cuda.device(x.device):
+        check(lib.d4w_stencil_zero_f32(dev.ptr(x), h, w, k.ctypes.data_as(_P_DOUBLE), k.shape[0], k.shape[1], int(anchor[0]),
+                                       int(anchor[1]), dev.out_ptr(out), dev.stream_ptr(x)))
+    return out
+
+
+def gradient_oriented(image, direction):
+    """Three-point oriented difference -- reference improcess.py:143-169.  direction = (dft, dfx), non-negative integers:
+    dfx == 0: -(image[:, :-dft] - image[:, dft:]) [h, w - dft]; dft == 0: -(image[dfx:] - image[:-dfx]) [h - dfx, w]; else
+    -(image[dfx:-dfx, :-dft] - 0.5 image[2 dfx:, dft:] - 0.5 image[:-2 dfx, dft:]) [h - 2 dfx, w - dft].  (0, 0) gives the
+    reference's empty [h, 0]; a shift that leaves no output gives the empty array of that shape."""
+    _require_2d(image, "image")
+    try:
+        dft, dfx = (operator.index(d) for d in direction)
+    except TypeError:
+        raise ValueError("direction must be a pair of non-negative integers (dft, dfx)") from None
+    if dft < 0 or dfx < 0:
+        raise ValueError("direction must be a pair of non-negative integers (dft, dfx)")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    oh = h if dfx == 0 else max(h - dfx, 0) if dft == 0 else max(h - 2 * dfx, 0)
+    ow = max(w - dft, 0) if (dft or dfx) else 0
+    if oh == 0 or ow == 0:                                  # nothing to compute: no upload, no launch
+        if dev.is_tensor(image):
+            return torch.empty((oh, ow), dtype=torch.float32, device=image.device)
+        t = np.asarray(image).dtype
+        return np.empty((oh, ow), dtype=t if t.kind == "f" else np.float64)
+    x = dev.to_device_f32(image)
+    out = torch.empty((oh, ow), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib.d4w_gradient_oriented_f32(dev.ptr(x), h, w, dft, dfx, dev.out_ptr(out), dev.stream_ptr(x)))
+    return dev.like_input(out, image)
+
+
+# diagonal_filter + fliplr(diagonal_filter) of improcess.py:192-216: the two fftconvolve calls are linear in the kernel
+_DIAG5 = np.array([[1, 2, 2, 2, 1], [0, 1, 2, 1, 0], [0, 0, 0, 0, 0], [0, -1, -2, -1, 0], [-1, -2, -2, -2, -1]], dtype=np.float64)
+# weight_left + flip(weight_left, [0]) of improcess.py:251-255
+_DIAG3 = np.array([[1, -2, 1], [-2, 4, -2], [1, -2, 1]], dtype=np.float64)
+
+
+def detect_diagonal_edges(matrix, threshold):
+    """fftconvolve(matrix, D, 'same') + fftconvolve(matrix, fliplr(D), 'same') with the 5 x 5 diagonal kernel D -- reference
+    improcess.py:172-226 -- as one zero-border stencil with the summed kernel (a convolution: the kernel is applied flipped
+    in both axes).  `threshold` is accepted and unused, as in the reference.  NumPy input gives float64."""
+    _require_2d(matrix, "matrix")
+    y = _stencil_device(dev.to_device_f32(matrix), _DIAG5[::-1, ::-1], (2, 2))
+    if dev.is_tensor(matrix):
+        return y if matrix.is_cuda else y.to(matrix.device)
+    return dev.download(y, np.float64)
+
+
+def diagonal_edge_detection(img, threshold):
+    """conv2d(img, W, padding=1) + conv2d(img, flipud(W), padding=1) with the 3 x 3 diagonal kernel W -- reference
+    improcess.py:229-266 -- as one zero-border stencil with the summed kernel.  Like the reference it returns a CPU float32
+    torch.Tensor [h, w] for array input; a CUDA tensor gives a CUDA tensor.  `threshold` is unused, as in the reference."""
+    _require_2d(img, "img")
+    y = _stencil_device(dev.to_device_f32(img), _DIAG3, (1, 1))
+    if dev.is_tensor(img) and img.is_cuda:
+        return y
+    return y.cpu()
+
+
+def get_gaussian_kernel(ksize, sigma):
+    """cv2.getGaussianKernel(ksize, sigma) as OpenCV documents it, float64 [ksize]: exp(-(i - (ksize - 1) / 2)^2 / (2 sigma^2))
+    normalised to sum 1; sigma <= 0 means sigma = 0.3 ((ksize - 1) 0.5 - 1) + 0.8, except the fixed tables of ksize 1, 3, 5, 7."""
+    n = int(ksize)
+    fixed = {1: [1.0], 3: [0.25, 0.5, 0.25], 5: [0.0625, 0.25, 0.375, 0.25, 0.0625],
+             7: [0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125]}
+    if sigma <= 0 and n in fixed:
+        return np.array(fixed[n], dtype=np.float64)
+    s = float(sigma) if sigma > 0 else 0.3 * ((n - 1) * 0.5 - 1.0) + 0.8
+    i = np.arange(n, dtype=np.float64) - (n - 1) * 0.5
+    t = np.exp(-(i * i) / (2.0 * s * s))
+    return t / t.sum()
+
+
+def _is_uint8(a):
+    return a.dtype == (torch.uint8 if dev.is_tensor(a) else np.uint8)
+
+
+def _smooth_output(y, img):
+    """cv2's output depth is the input's: uint8 images are rounded half to even and saturated, floats keep their dtype."""
+    if not dev.is_tensor(img):
+        img = np.asarray(img)
+    if _is_uint8(img):
+        q = torch.round(y).clamp_(0.0, 255.0).to(torch.uint8)
+        if dev.is_tensor(img):
+            return q if img.is_cuda else q.to(img.device)
+        return q.cpu().numpy()
+    return dev.like_input(y, img)
+
+
+def _gaussian_blur_device(x, taps_y, taps_x):
+    h, w = x.shape
+    out = torch.empty_like(x)
+    if _n(x) == 0:
+        return out
+    ky, kx = int(taps_y.size), int(taps_x.size)
+    with torch.cuda.device(x.device):
+        nws = int(lib.d4w_gaussian_blur_ws_bytes(h, w, ky, kx))
+        ws = torch.empty(nws, dtype=torch.uint8, device=x.device) if nws else None
+        check(lib.d4w_gaussian_blur_f32(dev.ptr(x), h, w, taps_y.ctypes.data_as(_P_DOUBLE), taps_x.ctypes.data_as(_P_DOUBLE),
+                                        ky, kx, dev.out_ptr(out), dev.ptr(ws) if nws else None, dev.stream_ptr(x)))
+    return out
+
+
+def gaussian_filter(img, size, sigma):
+    """cv2.GaussianBlur(img, (size, size), sigma) -- reference improcess.py:370-392 -- by OpenCV's documented definition:
+    separable correlation with get_gaussian_kernel(size, sigma) along both axes, BORDER_REFLECT_101.  `size` must be odd
+    and positive.  float32 / float64 keep their dtype, uint8 comes back as uint8 (rounded half to even, saturated).
+    Unpinned: cv2 is not installed, and real OpenCV filters uint8 images in fixed point."""
+    _require_2d(img, "img")
+    try:
+        n = operator.index(size)
+    except TypeError:
+        raise ValueError("size must be an odd positive integer") from None
+    if n < 1 or n % 2 == 0:
+        raise ValueError("size must be an odd positive integer, got %d" % n)
+    taps = get_gaussian_kernel(n, float(sigma))
+    return _smooth_output(_gaussian_blur_device(dev.to_device_f32(img), taps, taps), img)
+
+
+def bilateral_space_weights(radius, sigma_space):
+    """exp(-(i^2 + j^2) / (2 sigma_space^2)) over the (2 radius + 1)^2 square, 0 outside the circle i^2 + j^2 <= radius^2."""
+    i = np.arange(-radius, radius + 1, dtype=np.float64)
+    rr = i[:, None] ** 2 + i[None, :] ** 2
+    return np.where(rr <= float(radius) ** 2, np.exp(-rr / (2.0 * float(sigma_space) ** 2)), 0.0)
+
+
+def bilateral_radius(diameter, sigma_space):
+    """diameter <= 0: max(round(1.5 sigma_space), 1) (sigma_space <= 0 counts as 1); else diameter // 2."""
+    ss = float(sigma_space) if sigma_space > 0 else 1.0
+    return max(int(round(1.5 * ss)), 1) if diameter <= 0 else int(diameter) // 2
+
+
+def bilateral_filter(img, diameter, sigma_color, sigma_space):
+    """cv2.bilateralFilter(img, diameter, sigma_color, sigma_space) -- reference improcess.py:319-344 -- by OpenCV's
+    documented definition: out(p) = sum_q w I(q) / sum_q w over the offsets q - p = (i, j) with i^2 + j^2 <= r^2,
+    w = exp(-(i^2 + j^2) / (2 sigma_space^2) - (I(q) - I(p))^2 / (2 sigma_color^2)), BORDER_REFLECT_101; a sigma <= 0 counts
+    as 1; r = diameter // 2, or max(round(1.5 sigma_space), 1) for diameter <= 0.  dtypes as gaussian_filter.
+    Unpinned: cv2 is not installed, and real OpenCV reads the float range weight from an interpolated table."""
+    _require_2d(img, "img")
+    try:
+        d = operator.index(diameter)
+    except TypeError:
+        raise ValueError("diameter must be an integer") from None
+    sc = float(sigma_color) if sigma_color > 0 else 1.0
+    ss = float(sigma_space) if sigma_space > 0 else 1.0
+    if not (np.isfinite(sc) and np.isfinite(ss)):
+        raise ValueError("sigma_color and sigma_space must be finite")
+    r = bilateral_radius(d, ss)
+    x = dev.to_device_f32(img)
+    h, w = x.shape
+    out = torch.empty_like(x)
+    if _n(x):
+        with torch.cuda.device(x.device):
+            sw = dev.to_device_f32(bilateral_space_weights(r, ss), x.device)
+            check(lib.d4w_bilateral_f32(dev.ptr(x), h, w, r, dev.ptr(sw), sc, dev.out_ptr(out), dev.stream_ptr(x)))
+    return _smooth_output(out, img)

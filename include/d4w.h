@@ -582,6 +582,43 @@ size_t d4w_radon_ws_bytes(int h, int w, int ntheta);
 int d4w_radon_f32(const float* img, int h, int w, const double* theta_deg_host, int ntheta, float* out, void* ws,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Edge stencils, Gaussian blur and bilateral filter (das4whales_amd/csrc/edges.hip): the image operators of
+ * improcess.py outside the Gabor detector.  Images are row-major float32 [h][w] on the DEVICE, out must not alias img,
+ * h w <= INT32_MAX.  Every output element is written by one thread in a fixed order: run-to-run bit-identical.
+ *
+ * d4w_stencil_zero_f32: out[y][x] = sum_ij kernel[i][j] img[y + i - anchor_y][x + j - anchor_x] with ZEROS outside the
+ *   image (d4w_filter2d_f32 reflects); kernel = HOST float64 [kh][kw], kh, kw <= 7, anchor inside the kernel.  Replaces the
+ *   two scipy.signal.fftconvolve(mode='same') calls of improcess.detect_diagonal_edges (improcess.py:172-226; pass the
+ *   summed kernel flipped in both axes, anchor = centre) and the two conv2d(padding=1) calls of
+ *   improcess.diagonal_edge_detection (improcess.py:229-266; the summed 3 x 3 kernel, anchor (1, 1)).
+ * d4w_gradient_oriented_f32: improcess.gradient_oriented (improcess.py:143-169), direction = (dft, dfx) >= 0:
+ *   dfx = 0: out[h][w - dft]         = -(img[y][x] - img[y][x + dft])
+ *   dft = 0: out[h - dfx][w]         = -(img[y + dfx][x] - img[y][x])
+ *   else:    out[h - 2 dfx][w - dft] = -(img[y + dfx][x] - 0.5 img[y + 2 dfx][x + dft] - 0.5 img[y][x + dft])
+ *   (0, 0) and shifts that leave no output write nothing (out may then be NULL).
+ * d4w_gaussian_blur_f32: cv2.GaussianBlur's arithmetic for float images (improcess.gaussian_filter, improcess.py:370-392):
+ *   out = columns(taps_y) of rows(taps_x) of img, correlation with the anchor at the centre, BORDER_REFLECT_101 (repeated
+ *   for images smaller than the kernel).  taps = HOST float64, odd lengths ky, kx; the caller computes them (OpenCV's
+ *   getGaussianKernel).  ky, kx <= 31: one launch, ws unused (d4w_gaussian_blur_ws_bytes = 0, ws may be NULL); larger: two
+ *   launches through ws = DEVICE scratch of d4w_gaussian_blur_ws_bytes(h, w, ky, kx) bytes.  NOT d4w_gaussian_filter_f32,
+ *   which is scipy.ndimage.gaussian_filter of the mask designers.
+ * d4w_bilateral_f32: cv2.bilateralFilter by its documented definition (improcess.bilateral_filter, improcess.py:319-344):
+ *   out(p) = sum_q w I(q) / sum_q w over the offsets of the (2 radius + 1)^2 square, BORDER_REFLECT_101,
+ *   w = space_w[q - p] exp(-(I(q) - I(p))^2 / (2 sigma_color^2)); space_w = DEVICE float32 [(2 radius + 1)^2], the
+ *   caller's spatial weights, 0 at the offsets outside the circle (skipped); sigma_color > 0.  radius <=
+ *   d4w_bilateral_max_tiled_radius() (15) runs from an LDS tile, larger radii (<= 1024) from global memory.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_stencil_zero_f32(const float* img, int h, int w, const double* kernel_host, int kh, int kw, int anchor_y,
+                         int anchor_x, float* out, void* stream);
+int d4w_gradient_oriented_f32(const float* img, int h, int w, int dft, int dfx, float* out, void* stream);
+size_t d4w_gaussian_blur_ws_bytes(int h, int w, int ky, int kx);
+int d4w_gaussian_blur_f32(const float* img, int h, int w, const double* taps_y_host, const double* taps_x_host, int ky,
+                          int kx, float* out, void* ws, void* stream);
+int d4w_bilateral_max_tiled_radius(void);
+int d4w_bilateral_f32(const float* img, int h, int w, int radius, const float* space_w, double sigma_color, float* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
