@@ -163,6 +163,11 @@ def _load():
                                           c_void_p, c_void_p]),
         "d4w_bilateral_max_tiled_radius": (c_int, []),
         "d4w_bilateral_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
+        "d4w_loc_solve_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+        "d4w_loc_misfit_grid_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_double, c_void_p, c_int, c_void_p, c_int,
+                                            ctypes.c_double, c_void_p, c_void_p, c_void_p]),
+        "d4w_loc_arrival_times_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch: fail loudly

@@ -619,6 +619,36 @@ int d4w_bilateral_max_tiled_radius(void);
 int d4w_bilateral_f32(const float* img, int h, int w, int radius, const float* space_w, double sigma_color, float* out,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Least-squares localisation (das4whales_amd/csrc/loc.hip): the reference's loc.py, batched.  float64 throughout; every
+ * pointer is DEVICE memory unless marked otherwise; cable_pos = [nch][3] (x, y, z in metres), Ti = [ncalls][nch] arrival
+ * times in seconds where NaN means "no pick on this channel"; c0 > 0.  Every output element is written by one thread and
+ * every sum has a fixed order: run-to-run bit-identical.
+ *
+ * d4w_loc_solve_f64: loc.solve_lq (loc.py:57-128) for ncalls calls at once, one workgroup per call.  Nbiter damped
+ *   Gauss-Newton steps on n = [x, y, z, t0] (z held with fix_z): rows of G = cos th cos ph / c0, cos th sin ph / c0,
+ *   sin th / c0 (absent with fix_z), 1 with th = atan2(|z_w - z_c|, r), ph = atan2(y_w - y_c, x_w - x_c);
+ *   dn = (G^T G + 1e-5 I)^-1 G^T (Ti - t0 - R / c0); n += 0.7 dn in the first four iterations, n += dn after.
+ *   first_guess = [ncalls][4], or NULL for the reference's [40000, 23000, -60, min of the call's valid Ti] (loc.py:86).
+ *   history [ncalls][Nbiter][4] = n after every iteration (may be NULL when Nbiter = 0), n_out [ncalls][4] = the last one.
+ *   At n_out, over the channels that carry a pick: gtg [ncalls][p][p] = G^T G without the regularisation (p = 3 with fix_z,
+ *   else 4) -- the matrix loc.calc_covariance_matrix (loc.py:156-191) rebuilds --, ssr [ncalls] = the sum of squared
+ *   residuals (loc.cal_variance_residuals, loc.py:131-153, divides it by npick - p) and npick [ncalls] (int32).  Nbiter = 0
+ *   evaluates these at first_guess.  A call without a pick gives NaN rows in history and n_out, zeros elsewhere.
+ * d4w_loc_misfit_grid_f64: for every call and every node (xs[ix], ys[iy], z) of a grid, the best emission time
+ *   t0 = mean over the picked channels of e = Ti - |cable - node| / c0 and rms = sqrt(mean (e - t0)^2).
+ *   rms, t0 = [ncalls][ny][nx]; NaN for a call without a pick.  ncalls <= 65535.
+ * d4w_loc_arrival_times_f64: loc.calc_arrival_times (loc.py:13-25) for npos positions at once:
+ *   out [npos][nch] = t0[p] + |cable - pos[p]| / c0, pos = [npos][3], t0 = [npos].  npos <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_loc_solve_f64(const double* cable_pos, int nch, const double* Ti, int ncalls, double c0, int nbiter, int fix_z,
+                      const double* first_guess, double* history, double* n_out, double* gtg, double* ssr, int* npick,
+                      void* stream);
+int d4w_loc_misfit_grid_f64(const double* cable_pos, int nch, const double* Ti, int ncalls, double c0, const double* xs, int nx,
+                            const double* ys, int ny, double z, double* rms, double* t0, void* stream);
+int d4w_loc_arrival_times_f64(const double* cable_pos, int nch, const double* pos, const double* t0, int npos, double c0,
+                              double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
