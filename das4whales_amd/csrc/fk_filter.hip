@@ -3447,21 +3447,24 @@ __global__ __launch_bounds__(kThreads) void analytic_onesided(float2* __restrict
     }
 }
 
-__global__ __launch_bounds__(kThreads) void analytic_combine_z(const float2* __restrict__ z, float* __restrict__ y, int ns,
-                                                                int mode, const float* __restrict__ var, float fscale) {
+// The real part of the analytic signal is the sample itself (x), not its transformed-and-back copy in z (off by ~1e-7 max|x|,
+// which is the whole signal of a row that is mostly offset): only the imaginary part comes from z.
+__global__ __launch_bounds__(kThreads) void analytic_combine_z(const float* __restrict__ x, const float2* __restrict__ z,
+                                                                float* __restrict__ y, int ns, int mode,
+                                                                const float* __restrict__ var, float fscale) {
     const size_t base = (size_t)blockIdx.y * ns;
     const int nout = (mode == 3) ? ns - 1 : ns;
     float* yr = y + (size_t)blockIdx.y * nout;
     const float inv_var = (mode == 2 || mode == 4) ? 1.0f / var[blockIdx.y] : 0.f;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nout; i += gridDim.x * blockDim.x) {
-        const float2 a = z[base + i];
+        const float2 a = make_float2(x[base + i], z[base + i].y);
         float v;
         if (mode == 0) v = sqrtf(fmaf(a.x, a.x, a.y * a.y));
         else if (mode == 1) v = a.y;
         else if (mode == 2) v = 10.0f * log10f(fmaf(a.x, a.x, a.y * a.y) * inv_var);
         else if (mode == 4) v = sqrtf(fmaf(a.x, a.x, a.y * a.y) * inv_var);
         else {
-            const float2 p = c_mulc(z[base + i + 1], a);
+            const float2 p = c_mulc(make_float2(x[base + i + 1], z[base + i + 1].y), a);
             v = atan2f(p.y, p.x) * fscale;
         }
         yr[i] = v;
@@ -3532,7 +3535,7 @@ int d4w_analytic_long_f32(const float* x, float* y, int nx, int ns, int mode, co
         if (rc) return rc;
         D4W_LAUNCH(analytic_onesided, grid, dim3(kThreads), 0, stream, z, ns, pl->N1, pl->N2, (const int*)pl->d_k1, (const int*)pl->d_k2);
         if ((rc = d4w_fkd_time_inv_f32(pl, h, stream))) return rc;
-        D4W_LAUNCH(analytic_combine_z, grid, dim3(kThreads), 0, stream, (const float2*)z, y, ns, mode, var, (float)(fs / (2.0 * M_PI)));
+        D4W_LAUNCH(analytic_combine_z, grid, dim3(kThreads), 0, stream, x, (const float2*)z, y, ns, mode, var, (float)(fs / (2.0 * M_PI)));
         return D4W_OK;
     }
     // Shapes with specialised f-k kernels: the time phase of the packed plan (pass A MODE 1: n1 transform of the real rows),

@@ -256,8 +256,8 @@ __global__ __launch_bounds__(kAnMaxThreads) void analytic_rows(RowFftDev F, cons
             const float2 h = tile[i >> 1];
             return make_float2(xr[i], ((i & 1) ? h.y : h.x) * scale);
         }
-        return c_scale(tile[i], scale);
-    };
+        return make_float2(xr[i], tile[i].y * scale);                 // the real part of the analytic signal IS the sample: not its
+    };                                                                // transformed-and-back copy (off by ~1e-7 max|x|: a row offset)
     if (mode == kAnIfreq) {
         float* yr = y + (size_t)blockIdx.x * (ns - 1);
         for (int i = tid; i < ns - 1; i += nthr) yr[i] = an_ifreq(zat(i), zat(i + 1), fscale);

@@ -8,6 +8,7 @@ import pytest
 import scipy.signal as sps
 
 from oracle import d4w_oracle as orc
+from tests import analytic_cases as ac
 from tests.emu_util import load_emu, vp
 
 TOL = 1e-5
@@ -396,8 +397,11 @@ def test_argument_errors(emu):
     assert emu.d4w_stft_mag_f32(vp(x), vp(y), vp(y), 2, 64, 16, 4, 0, 9, None) == -1                # bin range
 
 
-@pytest.mark.parametrize("nx,ns", [(3, 480), (2, 2 * 3 * 5 * 7 * 11), (5, 96), (37, 2 * 41), (7, 2 * 3 * 67), (3, 481), (5, 405), (2, 83),
-                                   (4, 1091), (18, 48), (100, 600), (8, 480), (154, 48), (1102, 48)])
+LONG_PATH_SHAPES = [(3, 480), (2, 2 * 3 * 5 * 7 * 11), (5, 96), (37, 2 * 41), (7, 2 * 3 * 67), (3, 481), (5, 405), (2, 83),
+                    (4, 1091), (18, 48), (100, 600), (8, 480), (154, 48), (1102, 48)]
+
+
+@pytest.mark.parametrize("nx,ns", LONG_PATH_SHAPES)
 def test_analytic_long_row_path(emu, nx, ns):
     """The HBM four-step path (used for rows beyond one workgroup's LDS) on small rows: all four
     modes agree with the single-workgroup kernel and the oracle.  Row lengths with a prime factor > 31 (2 x 41, 2 x 3 x 67)
@@ -574,3 +578,47 @@ def test_fuzz_analytic_any_row_length(emu):
             ok(emu, emu.d4w_analytic_long_f32(vp(x), vp(y), nx, ns, mode, None, ctypes.c_double(200.0), vp(ws), None))
             assert rel(y, ref) < TOL, ("long-row path", ns, mode)
         done += 1
+
+
+def _guarded(nx, nout):
+    """An [nx, nout] float32 output in front of NaNs that a kernel must leave alone (a sample more per row stays inside)."""
+    buf = np.full(nx * nout + ac.GUARD + nx, np.nan, dtype=np.float32)
+    return buf, buf[:nx * nout].reshape(nx, nout)
+
+
+@pytest.mark.parametrize("path", ["single workgroup", "long rows"])
+@pytest.mark.parametrize("nx,ns", LONG_PATH_SHAPES)
+def test_instant_freq_of_many_rows_vs_float64(emu, nx, ns, path):
+    """Mode 3 is the only mode whose output rows (ns - 1) are shorter than its input rows: several rows at once, every row a
+    tone of its own carrier (10 .. 60 Hz by r % 6, neighbours 10 Hz apart), through the single-workgroup kernel and through
+    the long-row path (analytic_combine, analytic_combine_z, the specialised plan's inverse pass + combine), against
+    diff(unwrap(angle(scipy.signal.hilbert))) in float64: the conditioned bar d w < TOL fs / 2 on every sample, the plain
+    bar 5 TOL fs / 2 where the envelope is above a fifth of its maximum, the row medians to 0.1 Hz; nothing written past
+    the nx (ns - 1) outputs."""
+    x = ac.spread_tones(nx, ns)
+    z, _ = ac.reference(x)
+    buf, y = _guarded(nx, ns - 1)
+    if path == "long rows":
+        emu.d4w_analytic_long_ws_bytes.restype = ctypes.c_size_t
+        ws = np.empty(emu.d4w_analytic_long_ws_bytes(nx, ns), dtype=np.uint8)
+        ok(emu, emu.d4w_analytic_long_f32(vp(x), vp(y), nx, ns, 3, None, ctypes.c_double(ac.FS), vp(ws), None))
+    else:
+        ok(emu, emu.d4w_analytic_f32(vp(x), vp(y), nx, ns, 3, None, ctypes.c_double(ac.FS), None))
+    assert np.all(np.isnan(buf[nx * (ns - 1):])), "wrote past the [nx, ns - 1] output"
+    ac.check_ifreq(y, z, ac.FS, range(nx), need_share=None)
+
+
+@pytest.mark.parametrize("nx,ns", LONG_PATH_SHAPES)
+def test_envelope_over_std_long_row_path(emu, nx, ns):
+    """Mode 4 (|z| / std, improcess.trace2image) through d4w_analytic_long_f32 -- generic even rows, odd rows, Bluestein
+    rows and the specialised plan's fused epilogue -- against |scipy.signal.hilbert| / sqrt(np.var) in float64."""
+    rng = np.random.default_rng(ns)
+    x = (rng.standard_normal((nx, ns)) + 0.2).astype(np.float32)
+    z, var64 = ac.reference(x)
+    var = var64.astype(np.float32)
+    emu.d4w_analytic_long_ws_bytes.restype = ctypes.c_size_t
+    ws = np.empty(emu.d4w_analytic_long_ws_bytes(nx, ns), dtype=np.uint8)
+    buf, y = _guarded(nx, ns)
+    ok(emu, emu.d4w_analytic_long_f32(vp(x), vp(y), nx, ns, 4, vp(var), ctypes.c_double(ac.FS), vp(ws), None))
+    assert np.all(np.isnan(buf[nx * ns:]))
+    ac.check_mode(4, y, z, var.astype(np.float64))
