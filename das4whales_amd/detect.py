@@ -1,13 +1,16 @@
 """detect -- MI355X-native mirror of das4whales.detect (reference: src/das4whales/detect.py).
 
 Templates are generated on the host in float64 (a few hundred samples); correlations run in the
-HIP library (include/d4w.h: d4w_row_stats_f32, d4w_xcorr_f32)."""
+HIP library (include/d4w.h: d4w_row_stats_f32 / d4w_row_stats_prefix_f32 for the normalisation; d4w_xcorr_mm_tail_f32,
+d4w_xcorr_fft_cont_f32 or d4w_xcorr_lens_f32 for the correlation; d4w_xcorr_dc_tail_rows_f32 where the zero-padded templates'
+tail takes a second pass -- _matched_filter chooses)."""
 import numpy as np
 import torch
 
 import collections.abc
 
 from . import _device as dev
+from . import dsp
 from ._lib import lib, check
 from .dsp import _cache_lock
 
@@ -91,7 +94,7 @@ def _row_stats_cached(x, prefix=False):
     """(mean, max|.|) of the rows of a CUDA tensor, remembered while the SAME tensor (identity and version counter) is asked
     again: the reference's scripts call compute_cross_correlogram once per template on one block
     (scripts/main_mfdetect.py:79-80), which would read it twice just for the normalisation.  prefix=True: (mean, max|.|,
-    prefix maxima) from one launch (d4w_row_stats_prefix_f32; what _apply_tails decides on)."""
+    prefix maxima) from one launch (d4w_row_stats_prefix_f32; what _matched_filter decides the tail per row on)."""
     import weakref
     nx, ns = x.shape
     # per stream: statistics formed on one stream are not ordered before a kernel of another
@@ -290,10 +293,12 @@ class Threshold:
         return self.scale * float(self.value.cpu().reshape(-1)[0])
 
 
-def xcorr_continuation_ok(taps_list, ns):
-    """Whether _xcorr_device(..., cont=...) applies: the matrix-core form, or two templates that run the fused overlap-save kernel."""
+def xcorr_continuation_ok(taps_list, ns, how=None):
+    """Whether _xcorr_device(..., cont=...) applies: the matrix-core form, or two templates that run the fused overlap-save kernel.
+    how: _xcorr_method(taps_list, ns, "auto") when the caller has resolved it already."""
     import os
-    how = _xcorr_method(taps_list, ns, "auto")
+    if how is None:
+        how = _xcorr_method(taps_list, ns, "auto")
     if how == "mm":
         return True
     return (how == "fft" and len(taps_list) == 2
@@ -359,7 +364,7 @@ def _template_parts(template):
 def _normalised_support(template):
     """detect.py:158: (template - mean) / max|template| over the zero-padded length; returns the
     non-zero support of the ORIGINAL template (the constant -mean/max tail on the padded part is
-    handled by _tail_coef / d4w_xcorr_mm_tail_f32 / d4w_xcorr_dc_tail_f32)."""
+    handled by _tail_coef and _matched_filter)."""
     return _template_parts(template)[0]
 
 
@@ -378,35 +383,68 @@ def _tail_coef(template):
 TAIL_EPS = 1e-6
 
 
-def _prefix_max(x, mean):
-    """max_j |sum_{i<j} (x - mean)| per row (d4w_row_prefix_max_f32): one read of x, shared by all templates."""
-    nx, ns = x.shape
-    with torch.cuda.device(x.device):
-        pm = torch.empty(nx, dtype=torch.float32, device=x.device)
-        check(lib.d4w_row_prefix_max_f32(dev.ptr(x), nx, ns, dev.ptr(mean), dev.ptr(pm), dev.stream_ptr(x)))
-    return pm
-
-
-def _apply_tails(x, stats, outs, taps, coefs, row_max, exact_tail=None, pmax=None):
-    """Adds the DC-tail term of every template with a non-zero coefficient to its correlogram in place.  exact_tail None:
-    per-row decision (TAIL_EPS) where the correlator left its row maxima, every row otherwise; True: every row; False:
-    none.  Row maxima of the rows that changed are formed again by the kernel.  pmax: the rows' prefix maxima when the
-    caller has them already (dsp.FkPlan.apply_stats_prefix)."""
+def _tail_form(taps, coefs, ns, exact_tail=None):
+    """(how, form): the correlator a block of ns-sample rows runs on (_xcorr_method) and how its zero-padded templates' DC
+    tails (detect.py:158) are added -- None (no non-zero coefficient, or exact_tail=False), "kernel" (inside the matrix-core
+    correlator, _tails_in_kernel), "rows" (second pass, decided per row by TAIL_EPS: exact_tail=None on the matrix-core
+    form, the one that leaves row maxima) or "all" (second pass, every row).  The ONE place where the form is chosen."""
+    how = _xcorr_method(taps, ns, "auto")                   # decided once (an override that does not apply warns once)
     if exact_tail is False or not any(c != 0.0 for c in coefs):
-        return
+        return how, None
+    if _tails_in_kernel(taps, coefs, ns, how):
+        # round 6: the term is formed inside the correlator (prefix sums in its sample-conversion phase) -- exact on every row,
+        # one pass over the block, no per-row decision
+        return how, "kernel"
+    return how, "rows" if exact_tail is None and how == "mm" else "all"
+
+
+def _needs_prefix_max(taps, coefs, ns):
+    """Whether _matched_filter(..., exact_tail=None) will read the rows' prefix maxima at this shape: who forms the row
+    statistics ahead of it (dsp._fk_apply_stats(..., prefix=)) forms them only then."""
+    return _tail_form(taps, coefs, ns)[1] == "rows"
+
+
+def _matched_filter(x, taps, coefs, exact_tail=None, stats=None, next_head=None, want_row_max=False):
+    """Peak-normalised correlograms of the rows of x (float32 CUDA [nx, ns]) with the templates' supports `taps`, the DC tails
+    of their zero-padded originals (coefs: _tail_coef; exact_tail as in compute_cross_correlograms) included
+    -> (correlograms, row maxima or None).
+    stats: (mean, maxabs[, prefix maxima]) of x as dsp._fk_apply_stats leaves them; what is missing comes from
+    _row_stats_cached.  next_head: [nx, >= longest support - 1] rows that continue x (stream.FileStream): the last lags
+    read them in place where a continuation applies (xcorr_continuation_ok), else [x | head] is correlated and cropped;
+    normalisation and tails stay those of x.  want_row_max: also return max over the lags per template and row where the
+    matrix-core correlator leaves it; without it that epilogue runs only for the per-row tail decision."""
     nx, ns = x.shape
-    mean, mx = stats
-    by_row = exact_tail is None and row_max is not None and len(row_max) == len(outs)
-    pm = (pmax if pmax is not None else _prefix_max(x, mean)) if by_row else None
-    with torch.cuda.device(x.device):
-        for k, (o, tp, c) in enumerate(zip(outs, taps, coefs)):
-            if c == 0.0:
-                continue
-            rm = row_max[k] if row_max is not None and len(row_max) == len(outs) else None
-            check(lib.d4w_xcorr_dc_tail_rows_f32(dev.ptr(x), nx, ns, dev.ptr(mean), dev.ptr(mx), float(c), len(tp),
-                                                 dev.out_ptr(o), dev.ptr(pm) if by_row else None,
-                                                 dev.out_ptr(rm) if rm is not None else None,
-                                                 TAIL_EPS if by_row else 0.0, dev.stream_ptr(x)))
+    how, form = _tail_form(taps, coefs, ns, exact_tail)
+    n_next = max(len(t) for t in taps) - 1 if next_head is not None else 0
+    cont, src = None, x
+    if n_next > 0:
+        if next_head.is_cuda and next_head.dtype == torch.float32 and next_head.stride(1) == 1 and xcorr_continuation_ok(taps, ns, how):
+            cont = (next_head, n_next)
+        else:
+            # the padding must enter de-meaned like the block's own samples (the kernel subtracts the mean from every
+            # sample it reads); the epilogues do not apply to the widened rows
+            src = dsp._concat_cols([x, next_head[:, :n_next]])
+            if form is not None:
+                form = "all"
+    if stats is None or (form == "rows" and len(stats) < 3):
+        stats = _row_stats_cached(x, prefix=form == "rows")
+    rmax = [] if src is x and (want_row_max or form == "rows") else None
+    outs = _xcorr_device(src, taps, normalize=True, method=how, stats=stats[:2], cont=cont, row_max=rmax,
+                         tails=coefs if form == "kernel" else None)
+    if src is not x:
+        outs = [dsp._copy_cols(c[:, :ns], torch.empty_like(x)) for c in outs]
+    if form in ("rows", "all"):
+        # a row is left without the term only where it cannot exceed TAIL_EPS of the row's own largest correlation ("rows");
+        # the kernel forms the row maxima of the rows it changes again
+        by_row = form == "rows"
+        with torch.cuda.device(x.device):
+            for k, (o, tp, c) in enumerate(zip(outs, taps, coefs)):
+                if c != 0.0:
+                    check(lib.d4w_xcorr_dc_tail_rows_f32(dev.ptr(x), nx, ns, dev.ptr(stats[0]), dev.ptr(stats[1]), float(c), len(tp),
+                                                         dev.out_ptr(o), dev.ptr(stats[2]) if by_row else None,
+                                                         dev.out_ptr(rmax[k]) if rmax else None,
+                                                         TAIL_EPS if by_row else 0.0, dev.stream_ptr(x)))
+    return outs, rmax or None
 
 
 def _nan_dead_rows(xd, outs):
@@ -421,7 +459,7 @@ def compute_cross_correlograms(data, templates, exact_tail=None, zero_rows=None)
     """Several templates against one block (detect.compute_cross_correlogram for each) -- what
     scripts/main_mfdetect.py:79-80 does with two separate calls.  exact_tail: True / False forces /
     skips the DC-tail term of the zero-padded template (detect.py:158) on every row; None (default) decides per row
-    on the data and leaves out only what cannot exceed TAIL_EPS of the row's largest correlation (_apply_tails).
+    on the data and leaves out only what cannot exceed TAIL_EPS of the row's largest correlation (_matched_filter).
     zero_rows: "zeros" (default) / "nan" -- what an all-zero row gives; "nan" is the reference's 0 / 0
     (default "nan" under das4whales_amd.set_strict_reference(True))."""
     if zero_rows is None:
@@ -438,21 +476,8 @@ def _correlograms(data, templates, exact_tail):
     if getattr(data, "ndim", 0) != 2:
         raise ValueError("data must be a 2-D [channel x time] array")
     xd = dev.to_device_f32(data)
-    nx, ns = xd.shape
-    taps = [_normalised_support(t) for t in templates]
-    coefs = [_tail_coef(t) for t in templates]
-    tails = exact_tail is not False and any(c != 0.0 for c in coefs)
-    how = _xcorr_method(taps, ns, "auto")                   # decided once (an override that does not apply warns once)
-    if tails and _tails_in_kernel(taps, coefs, ns, how):
-        # round 6: the term is formed inside the correlator (prefix sums in its sample-conversion phase) -- exact on every row,
-        # one pass over the block, no per-row decision
-        return xd, _xcorr_device(xd, taps, normalize=True, method=how, stats=_row_stats_cached(xd), tails=coefs)
-    by_row = tails and exact_tail is None and how == "mm"      # the form that leaves row maxima
-    stats = _row_stats_cached(xd, prefix=by_row) if tails else None
-    rmax = [] if by_row else None
-    outs = _xcorr_device(xd, taps, normalize=True, method=how, stats=stats[:2] if stats else None, row_max=rmax)
-    if tails:
-        _apply_tails(xd, stats[:2], outs, taps, coefs, rmax, exact_tail, pmax=stats[2] if by_row else None)
+    # no row maxima asked for: the in-kernel tail runs the kernel instance without that epilogue
+    outs, _ = _matched_filter(xd, [_normalised_support(t) for t in templates], [_tail_coef(t) for t in templates], exact_tail=exact_tail)
     return xd, outs
 
 

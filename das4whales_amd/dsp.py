@@ -161,7 +161,7 @@ class FkPlan:
 
     def apply_stats_prefix(self, x, out=None, taper=False):
         """apply_stats() that also returns the rows' prefix maxima max_j |sum_{i<j} (y - mean)| (d4w_row_prefix_max_f32: what
-        bounds the DC-tail term of a zero-padded template, detect._apply_tails).  Where the plan would sweep the result for the
+        bounds the DC-tail term of a zero-padded template, detect._matched_filter).  Where the plan would sweep the result for the
         statistics anyway (d4w_fk_stats_in_epilogue == 0: the 60-s file shapes) one launch forms all three, the second
         sweep of a row served by L2."""
         if int(lib.d4w_fk_stats_in_epilogue(self._h)):

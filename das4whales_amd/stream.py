@@ -42,7 +42,6 @@ class FileStream:
         # DC tail of a zero-padded full-length template (detect.py:158), applied per file exactly as
         # detect.compute_cross_correlograms does (0 for support-only vectors)
         self.tail = [detect._tail_coef(t) for t in templates]
-        self.lmax = max((len(t) for t in self.taps), default=1)
         self.fk_mask = fk_mask
         self._raw = []          # raw files waiting for their right halo: [(index, tensor)]
         self._prev_tail = dev.to_device_f32(prev_tail) if prev_tail is not None else None   # last `halo` raw samples of the file before self._raw[0]
@@ -90,78 +89,24 @@ class FileStream:
             if self.halo > 0 else None
         stats = None
         if self.fk_mask is not None:
-            # the row means / maxima the matched filter normalises by come out of the f-k filter's last pass
-            # (and, for zero-padded templates, the prefix maxima their DC-tail term is decided on)
-            y, stats = dsp._fk_apply_stats(y, self.fk_mask, prefix=self._want_prefix(y.shape[1])) if self.taps \
-                else (dsp.fk_filter_filt(y, self.fk_mask), None)
+            # the row statistics the matched filter normalises by (and, where it will ask for them, decides the zero-padded
+            # templates' DC tail on) come out of the f-k filter's last pass
+            y, stats = dsp._fk_apply_stats(y, self.fk_mask, prefix=detect._needs_prefix_max(self.taps, self.tail, y.shape[1])) \
+                if self.taps else (dsp.fk_filter_filt(y, self.fk_mask), None)
         if self._on_filtered is not None:
             self._on_filtered(idx, y)
         return idx, y, stats
 
-    def _tails_in_kernel(self, ns):
-        """Round 6: the zero-padded templates' DC tail is added inside the matrix-core correlator where that applies
-        (detect._tails_in_kernel) -- no prefix maxima, no second pass."""
-        return bool(self.taps) and detect._tails_in_kernel(self.taps, self.tail, ns, detect._xcorr_method(self.taps, ns, "auto"))
-
-    def _want_prefix(self, ns):
-        return any(c != 0.0 for c in self.tail) and not self._tails_in_kernel(ns)
-
     def _correlate(self, idx, y, next_head, stats=None):
-        """Correlograms of filtered file `y`, its last lags completed with `next_head` (or cut short); stats = (row means,
-        row maxima) of y when the f-k filter left them."""
+        """Correlograms of filtered file `y`, its last lags completed with `next_head` (or cut short); stats = the row
+        statistics of y when the f-k filter left them."""
         out = {"index": idx, "filtered": y}
-        if not self.taps:
-            return out
-        nx, ns = y.shape
-        from ._lib import lib, check
-        pm = None
-        if stats is not None:
-            mean, mx = stats[:2]
-            pm = stats[2] if len(stats) > 2 else None
-        else:
-            with torch.cuda.device(y.device):
-                mean = torch.empty(nx, dtype=torch.float64, device=y.device)
-                mx = torch.empty(nx, dtype=torch.float32, device=y.device)
-                if self._want_prefix(ns):
-                    pm = torch.empty(nx, dtype=torch.float32, device=y.device)
-                    check(lib.d4w_row_stats_prefix_f32(dev.ptr(y), nx, ns, dev.ptr(mean), dev.ptr(mx), dev.ptr(pm), dev.stream_ptr(y)))
-                else:
-                    check(lib.d4w_row_stats_f32(dev.ptr(y), nx, ns, dev.ptr(mean), dev.ptr(mx), dev.stream_ptr(y)))
-        if next_head is not None and self.lmax > 1 and next_head.is_cuda and next_head.dtype == torch.float32 \
-                and next_head.stride(1) == 1 and detect.xcorr_continuation_ok(self.taps, ns):
-            # rows continue into the next file: the kernel reads the head of the next file's rows in place (de-meaned
-            # like the file's own samples) -- no concatenated copy, no cropped copies of the correlograms
-            rmax = []
-            inker = self._tails_in_kernel(ns)
-            cs = detect._xcorr_device(y, self.taps, normalize=True, stats=(mean, mx), cont=(next_head, self.lmax - 1),
-                                      row_max=rmax, tails=self.tail if inker else None)
-            if len(rmax) == len(cs):
+        if self.taps:
+            # (a file without a successor -- the record's last -- gets its row maxima from the correlator's epilogue too)
+            out["correlograms"], rmax = detect._matched_filter(y, self.taps, self.tail, stats=stats, next_head=next_head,
+                                                               want_row_max=True)
+            if rmax is not None:
                 out["row_max"] = rmax        # max over the lags of every row, per template (detect.correlogram_max)
-            if inker:
-                out["correlograms"] = cs
-                return out
-        else:
-            if next_head is not None and self.lmax > 1:
-                # the padding must enter de-meaned like the file's own samples (the kernel subtracts the mean from
-                # every sample it reads)
-                ext = dsp._concat_cols([y, next_head[:, :self.lmax - 1]])
-            else:
-                ext = y
-            # (a file without a successor -- the record's last -- still gets its row maxima from the correlator's epilogue:
-            # the DC-tail decision per row and correlogram_max need no sweep of the correlograms then)
-            rmax = [] if ext is y else None
-            inker = ext is y and self._tails_in_kernel(ns)
-            cs = detect._xcorr_device(ext, self.taps, normalize=True, stats=(mean, mx), row_max=rmax, tails=self.tail if inker else None)
-            if rmax and len(rmax) == len(cs):
-                out["row_max"] = rmax
-            if inker:
-                out["correlograms"] = cs
-                return out
-            cs = [dsp._copy_cols(c[:, :ns], torch.empty_like(y)) if c.shape[1] != ns else c for c in cs]
-        # the DC tail of zero-padded templates, decided per row on the data (detect._apply_tails: the band-passed rows of
-        # a stream have prefix sums of a few samples' size and are left alone; the row maxima stay valid either way)
-        detect._apply_tails(y, (mean, mx), cs, self.taps, self.tail, out.get("row_max"), pmax=pm)
-        out["correlograms"] = cs
         return out
 
     # ------------------------------------------------------------------------------------------
@@ -189,7 +134,7 @@ class FileStream:
     def flush(self, next_head=None, next_filtered_head=None):
         """End of the stream: finish the files still waiting.  By default their right edge is a true record end;
         when the record continues elsewhere, next_head = the first `halo` raw samples of the following file and
-        next_filtered_head = the first lmax - 1 filtered samples of it (a tensor, or a callable returning one -- e.g.
+        next_filtered_head = the first (longest template support - 1) filtered samples of it (a tensor, or a callable returning one -- e.g.
         the wait on a receive posted earlier)."""
         done = []
         head = dev.to_device_f32(next_head)[:, :self.halo] if next_head is not None and self.halo > 0 else None

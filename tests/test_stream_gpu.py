@@ -1,6 +1,8 @@
 """GPU test of das4whales_amd.stream.FileStream: consecutive files processed as one
 continuous record.  Parity targets: the band-pass of every file equals the oracle's bp_filt of the
 CONCATENATED record; the correlogram's last lags continue into the next file."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -16,17 +18,25 @@ def rel(y, ref):
     return float(np.max(np.abs(np.asarray(y, dtype=np.float64) - ref)) / np.max(np.abs(ref)))
 
 
-@pytest.mark.parametrize("with_fk", [False, True])
-def test_stream_equals_concatenated_record(with_fk):
-    assert torch.cuda.is_available()
-    import das4whales_amd as dw
-    from das4whales_amd import stream
+@functools.lru_cache(maxsize=None)
+def _record():
+    """The 48 x 3000, four-file record, its templates and the reference band-pass of the whole record (formed once, read-only)."""
     rng = np.random.default_rng(31)
     nx, ns, nfiles = 48, 3000, 4
     rec = rng.standard_normal((nx, ns * nfiles)) + 0.3
     t = np.arange(ns) / FS
     hf = orc.gen_template_fincall(t, FS, 17.8, 28.8, 0.68)
     lf = orc.gen_template_fincall(t, FS, 14.7, 21.8, 0.78)
+    F = orc.bp_filt(rec, FS, 14, 30)                         # the reference filter on the whole record
+    for a in (rec, hf, lf, F):
+        a.setflags(write=False)
+    return nx, ns, nfiles, rec, hf, lf, F
+
+
+def _stream_against_the_record(with_fk, need_row_max):
+    import das4whales_amd as dw
+    from das4whales_amd import stream
+    nx, ns, nfiles, rec, hf, lf, F = _record()
     mask = np.ones((nx, ns)) if with_fk else None            # identity f-k mask: exercises the per-file f-k step
     st = stream.FileStream(FS, 14, 30, templates=[hf, lf], fk_mask=mask, halo=1024)
     results = []
@@ -36,7 +46,6 @@ def test_stream_equals_concatenated_record(with_fk):
         results += got
     results += st.flush()
     assert [r["index"] for r in results] == list(range(nfiles))
-    F = orc.bp_filt(rec, FS, 14, 30)                         # the reference filter on the whole record
     taps = [dw.detect._normalised_support(hf), dw.detect._normalised_support(lf)]
     filt = {r["index"]: r["filtered"].cpu().numpy().astype(np.float64) for r in results}
     for r in results:
@@ -63,17 +72,42 @@ def test_stream_equals_concatenated_record(with_fk):
             for c, rm in zip(r["correlograms"], r["row_max"]):
                 assert torch.equal(rm, c.max(dim=1).values)
                 assert dw.detect.correlogram_max(c, rm) == float(c.max()) == dw.detect.correlogram_max(c)
-        else:
+        elif need_row_max:
             raise AssertionError("every file of a stream carries the row maxima of its correlograms (round 5: the last one too)")
+    return dw, rec, ns, F
+
+
+@pytest.mark.parametrize("with_fk,tail", [(False, None), (True, None), (False, "pass"), (True, "pass")],
+                         ids=["False", "True", "False-pass", "True-pass"])
+def test_stream_equals_concatenated_record(with_fk, tail, monkeypatch):
+    """tail = "pass" (D4W_XCORR_TAIL): the two-pass form of the zero-padded templates' DC tail, decided per row for the two
+    continued files and for the last one -- on prefix maxima from the f-k filter's epilogue (with_fk) or from the
+    row-statistics launch."""
+    assert torch.cuda.is_available()
+    if tail is None:
+        monkeypatch.delenv("D4W_XCORR_TAIL", raising=False)
+    else:
+        monkeypatch.setenv("D4W_XCORR_TAIL", tail)
+    dw, rec, ns, F = _stream_against_the_record(with_fk, need_row_max=True)
     # a stand-alone file (the reference's per-file run) differs from the stream at the file edges
     alone = dw.dsp.bp_filt(rec[:, ns:2 * ns], FS, 14, 30)
     assert rel(alone, F[:, ns:2 * ns]) > 1e-3
 
 
+@pytest.mark.parametrize("method", ["fft", "direct"])
+def test_stream_on_the_other_correlator_forms(method, monkeypatch):
+    """D4W_XCORR_METHOD = "fft": the continuation through the overlap-save form (two templates, rows >= 1024 samples, supports
+    136 / 156 <= 161), which leaves no row maxima, so the DC-tail term goes on every row in a second pass; "direct": no
+    continuation -- concatenate with the next file's head, correlate, crop.  The reference omits the tail term: 3e-8 of the
+    correlogram on band-passed rows, far inside TOL.  These forms give no "row_max"."""
+    monkeypatch.setenv("D4W_XCORR_METHOD", method)
+    _stream_against_the_record(False, need_row_max=False)
+
+
 def test_stream_at_the_ooi_file_shape():
     """Three consecutive 11 020 x 12 000 files (BASELINE configs[4] geometry): the middle file's band-pass is the halo form
     (d4w_fir_fft_halo_f32, neighbours read in place), its correlograms continue into the third file
-    (d4w_xcorr_fft_cont_f32).  Rows are independent: eight of them against the oracle on the concatenated record."""
+    (d4w_xcorr_mm_tail_f32, the matrix-core kernel).  Rows are independent: eight of them against the oracle on the concatenated record."""
     import das4whales_amd as dw
     from das4whales_amd import stream
     nx, ns = 11020, 12000
