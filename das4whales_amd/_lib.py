@@ -6,6 +6,12 @@ missing (not built) the import fails loudly with the build command.
 import ctypes
 import os
 
+# torch first, always: it brings the HIP runtime it was built with, and libd4w.so (which needs libamdhip64.so.7 by soname) then
+# binds to that copy.  Loaded the other way round, libd4w.so pulls the system's runtime and torch still loads its own (it asks
+# for it under another file name): two HIP runtimes in one process, torch's memory and streams in one, these kernels in the
+# other.  `import das4whales_amd` before `import torch` did exactly that.
+import torch  # noqa: F401
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _PACKAGED = os.path.join(_HERE, "lib", "libd4w.so")
 # D4W_LIB: another build of the same library (probe builds with extra instrumentation, scripts/probe/fp_timing.sh).  Never

@@ -291,9 +291,12 @@ __global__ __launch_bounds__(kF2Threads) void filter2d_tile(const float* __restr
     const int walk = f2_walk(kh), kp = f2_kp(kh);
     const int prows = kF2TileH - kF2Rows + walk;       // patch rows incl. the zero rows the unrolled walk touches
     const int x0 = blockIdx.x * kF2TileW - kw / 2, y0 = blockIdx.y * kF2TileH - kh / 2;
+    // patch rows below the last one a stored output row reads (the tile's rows past the image) stay zero: they meet
+    // zero taps only, and a reflected row would carry a NaN or inf pixel into row groups that never read it
+    const int vrows = min(ph, h - (int)blockIdx.y * kF2TileH + kh - 1);
     for (int e = threadIdx.x; e < pw * prows; e += kF2Threads) {
         const int ty = e / pw, tx = e % pw;
-        tile[e] = (ty < ph) ? img[(size_t)reflect101(y0 + ty, h) * w + reflect101(x0 + tx, w)] : 0.f;
+        tile[e] = (ty < vrows) ? img[(size_t)reflect101(y0 + ty, h) * w + reflect101(x0 + tx, w)] : 0.f;
     }
     __syncthreads();
     const int tx = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: taps via SMEM
@@ -413,13 +416,14 @@ int d4w_filter2d_f32(const float* img, int h, int w, const float* kernel, int kh
     const size_t patch = (size_t)(kF2TileW + kw - 1) * (kF2TileH - kF2Rows + f2_walk(kh)) * sizeof(float);
     const size_t lds = std::max(patch, (size_t)kF2Split * kF2TileH * kF2TileW * sizeof(float));
     if (lds > 160 * 1024) return fail(D4W_EINVAL, "kernel %d x %d needs %zu bytes of LDS (limit 163840)", kh, kw, lds);
+    // above 64 KiB a kernel has to opt into its dynamic LDS size; a refused opt-in is this call's error, before any launch
+    if (lds > 64 * 1024) {
+        if (accumulate) D4W_HIP(hipFuncSetAttribute((const void*)filter2d_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        else D4W_HIP(hipFuncSetAttribute((const void*)filter2d_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
     float* Kp = (float*)ws;
     D4W_LAUNCH(f2_pad_kernel, dim3(64), dim3(kImThreads), 0, stream, kernel, kh, kw, Kp);
     const dim3 grid((w + kF2TileW - 1) / kF2TileW, (h + kF2TileH - 1) / kF2TileH);
-    if (lds > 64 * 1024) {
-        (void)hipFuncSetAttribute((const void*)filter2d_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)filter2d_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
     if (accumulate) D4W_LAUNCH(filter2d_tile<true>, grid, dim3(kF2Threads), lds, stream, img, h, w, (const float*)Kp, kh, kw, out);
     else D4W_LAUNCH(filter2d_tile<false>, grid, dim3(kF2Threads), lds, stream, img, h, w, (const float*)Kp, kh, kw, out);
     return D4W_OK;

@@ -833,14 +833,19 @@ def apply_smooth_mask(array, mask, sigma=1.5):
 
 
 def gabor_mask_pipeline(trf_fk, fs, dx, selected_channels, c0=1500., threshold=9100., threshold2=150.):
-    """scripts/main_gabordetect.py:78-166 without the plots."""
+    """scripts/main_gabordetect.py:78-166 without the plots.  A threshold may be a callable: it is handed the array it
+    applies to (fimage, score) and returns the number, for callers that place it by the data (a percentile)."""
     image = trace2image(trf_fk)
     theta_c0 = angle_fromspeed(c0, fs, dx, selected_channels)
     imagebin = binning(image, 1 / 10, 1 / 10)
     up, down = gabor_filt_design(theta_c0)
     fimage = filter2d(imagebin, up) + filter2d(imagebin, down)
+    if callable(threshold):
+        threshold = threshold(fimage)
     binary = fimage > threshold
     score = filter2d(binary.astype(float), up) + filter2d(binary.astype(float), down)
+    if callable(threshold2):
+        threshold2 = threshold2(score)
     mask = score > threshold2
     mask_sparse = binning(mask, 10, 10)
     masked_tr = apply_smooth_mask(np.asarray(trf_fk, dtype=np.float64), mask_sparse)

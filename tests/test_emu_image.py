@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import d4w_oracle as orc
+from tests import image_cases as ic
 from tests.emu_util import load_emu, vp
 
 TOL = 1e-5
@@ -81,6 +82,119 @@ def test_filter2d(emu, h, w, kh, kw):
     assert rel(out, ref) < TOL
     assert emu.d4w_filter2d_f32(vp(img), h, w, vp(ker), kh, kw, vp(out), 1, vp(ws), None) == 0      # accumulate
     assert rel(out, 2 * ref) < TOL
+
+
+def run_filter2d(emu):
+    emu.d4w_filter2d_ws_bytes.restype = sz
+
+    def run(img, ker, accumulate=0, out=None):
+        img, ker = f32(img), f32(ker)
+        (h, w), (kh, kw) = img.shape, ker.shape
+        out = np.empty_like(img) if out is None else out
+        ws = np.empty(emu.d4w_filter2d_ws_bytes(kh, kw), dtype=np.uint8)
+        assert emu.d4w_filter2d_f32(vp(img), h, w, vp(ker), kh, kw, vp(out), accumulate, vp(ws), None) == 0, emu.d4w_last_error()
+        return out
+    return run
+
+
+@pytest.mark.parametrize("h,w,kh,kw", ic.DIRECT)
+def test_filter2d_direct_form(emu, h, w, kh, kw):
+    """filter2d_tile: the smallest kernel without a matrix-core form, patches above 64 KiB and just under the 160 KiB
+    limit, ragged tiles, an even kernel height, a Gabor kernel of ksize 120 on a 0-255 image (tests/image_cases.py)."""
+    assert emu.d4w_filter2d_mm_eligible(kh, kw) == 0
+    e = ic.filter2d_rel(run_filter2d(emu), *ic.direct_case(h, w, kh, kw))
+    print("direct %s rel %.2e" % ((h, w, kh, kw), e))
+    assert e < TOL
+
+
+def test_filter2d_direct_form_accumulates(emu):
+    run = run_filter2d(emu)
+    img, k1 = ic.noise_case(10, 70, 3, 114)
+    k2 = ic.noise_case(11, 70, 3, 114)[1]
+    out = run(img, k1)
+    out = run(img, k2, accumulate=1, out=out)
+    ref = orc.filter2d(img.astype(np.float64), k1.astype(np.float64)) + orc.filter2d(img.astype(np.float64), k2.astype(np.float64))
+    assert rel(out, ref) < TOL
+
+
+@pytest.mark.parametrize("h,w,kh,kw", ic.WIDE[:2] + ic.TILE_EDGES + ic.RING_EDGES + ic.SHORT_IMAGES)
+def test_filter2d_matrix_core_edges(emu, h, w, kh, kw):
+    """filter2d_mm_rows: several workgroups per row block with kernels as deep as the prefetch ring, images that end on,
+    before and after a 256-column tile, kernel heights around the prefetch ring and the row ring, images shorter than the
+    kernel and than a row group."""
+    assert emu.d4w_filter2d_mm_eligible(kh, kw) == 1
+    e = ic.filter2d_rel(run_filter2d(emu), *ic.noise_case(h, w, kh, kw))
+    print("matrix cores %s rel %.2e" % ((h, w, kh, kw), e))
+    assert e < TOL
+
+
+def test_filter2d_value_ranges(emu):
+    print(ic.check_values(run_filter2d(emu)))
+
+
+@pytest.mark.parametrize("kh,kw", ic.NONFINITE)
+@pytest.mark.parametrize("bad", [np.nan, np.inf])
+def test_filter2d_one_nonfinite_pixel(emu, kh, kw, bad):
+    """One NaN or inf pixel spreads beyond its kh x kw window in both forms; what stays finite is right."""
+    n, e = ic.check_nonfinite(run_filter2d(emu), kh, kw, bad)
+    print("%s pixel, kernel %d x %d: %d of 8000 outputs non-finite, finite ones rel %.2e" % (bad, kh, kw, n, e))
+
+
+@pytest.mark.parametrize("h,w,oh,ow", ic.RESIZE)
+def test_resize_unstaged_branch_and_neighbours(emu, h, w, oh, ow):
+    """resize_rows reads global memory directly when a workgroup's 256 outputs span more than 4096 inputs; the span of
+    every case is taken from the oracle's weight table to prove which side of that threshold it is on."""
+    spans = ic.check_resize_side(w, ow)
+    rng = np.random.default_rng(w + ow)
+    x = f32(rng.standard_normal((h, w)))
+    emu.d4w_resize_ws_bytes.restype = sz
+
+    def resize(a):
+        y = np.empty((oh, ow), dtype=np.float32)
+        ws = np.empty(emu.d4w_resize_ws_bytes(h, w, oh, ow), dtype=np.uint8)
+        assert emu.d4w_resize_bilinear_aa_f32(vp(a), h, w, vp(y), oh, ow, vp(ws), None) == 0, emu.d4w_last_error()
+        return y
+    e = rel(resize(x), orc.resize_bilinear_aa(x.astype(np.float64), oh, ow))
+    print("resize %s spans %s rel %.2e" % ((h, w, oh, ow), spans[:3], e))
+    assert e < TOL
+    m = rng.random((h, w)) > 0.97
+    assert np.array_equal(resize(f32(m)) != 0, orc.resize_bilinear_aa(m.astype(np.float64), oh, ow) != 0)
+
+
+@pytest.mark.parametrize("n", ic.MINMAX_N)
+def test_minmax_forms_and_nonfinite_values(emu, n):
+    mm = np.zeros(2, dtype=np.float32)
+    for name, x in ic.minmax_cases(n):
+        assert emu.d4w_minmax_f32(vp(x), sz(n), vp(mm), None) == 0
+        ic.check_minmax(name, x, mm)
+
+
+def test_scale_constant_image_and_threshold_in_float64(emu):
+    x = np.full(700, 3.5, dtype=np.float32)
+    mm = np.zeros(2, dtype=np.float32)
+    y = np.zeros_like(x)
+    assert emu.d4w_minmax_f32(vp(x), sz(x.size), vp(mm), None) == 0
+    assert emu.d4w_scale_pixels_f32(vp(x), vp(y), sz(x.size), vp(mm), ctypes.c_double(255.0), None) == 0
+    with np.errstate(invalid="ignore"):
+        ref = orc.scale_pixels(x.astype(np.float64)) * 255
+    assert np.array_equal(np.isnan(y), np.isnan(ref)) and np.isnan(ref).all()
+    x, want = ic.threshold_inputs(0.1)
+    y = np.empty_like(x)
+    assert emu.d4w_threshold_f32(vp(x), vp(y), sz(x.size), ctypes.c_double(0.1), None) == 0
+    assert np.array_equal(y != 0, want)
+
+
+def test_filter2d_refuses_kernels_beyond_the_lds_before_any_launch(emu):
+    emu.d4w_filter2d_ws_bytes.restype = sz
+    img = f32(np.random.default_rng(3).standard_normal((8, 40)))
+    for kh, kw in ic.REFUSED:
+        ker = np.ones((kh, kw), dtype=np.float32)
+        out = np.full_like(img, 7.0)
+        ws = np.full(emu.d4w_filter2d_ws_bytes(kh, kw), 0x5a, dtype=np.uint8)
+        assert emu.d4w_filter2d_f32(vp(img), 8, 40, vp(ker), kh, kw, vp(out), 0, vp(ws), None) == -1
+        assert b"bytes of LDS" in emu.d4w_last_error()
+        assert np.all(out == 7.0) and np.all(ws == 0x5a)               # nothing ran: neither the padded kernel nor an output
+    assert ic.filter2d_rel(run_filter2d(emu), *ic.noise_case(8, 40, 3, 114)) < TOL
 
 
 def test_filter2d_rejects_oversized_kernel_and_inplace(emu):
