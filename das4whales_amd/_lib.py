@@ -80,6 +80,7 @@ def _load():
         "d4w_sosfiltfilt_ws_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
         "d4w_sosfiltfilt_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, P(ctypes.c_double), P(ctypes.c_double),
                                         c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+        "d4w_sosfiltfilt_last_form": (c_int, []),
         "d4w_sosfiltfilt_ends_ws_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
         "d4w_sosfiltfilt_ends_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                              c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -969,12 +969,16 @@ static int sos_prepare(const double* sos, const double* zi, int nsec, SosArgs& A
     return D4W_OK;
 }
 
+// which kernel and which state precision the calling thread's last zero-phase filter call dispatched (d4w_sosfiltfilt_last_form)
+static thread_local int g_sos_last_form = 0;
+
 // forward + backward launch of sos_pass_lanes: src rows -> t rows (all outputs, + the right-extension outputs in `edge`),
 // t rows -> the kept windows of the dst rows
 static int sos_lanes_both(int nsec, bool precise, const SosArgs& A, const SosArgsT<double>& Ad, SlRows src, SlRows tr, SlRows dst,
                           int ka0, int ka1, int kb0, int kb1, float* edge, int nrows, int n, int padlen, SlRows piv, float dcg2,
                           void* stream, int phase = 0) {
     const int G = nsec <= 8 ? 8 : 16;
+    g_sos_last_form = G + (precise ? 800 : 400);
     const dim3 lgrid(ceil_div(nrows, (kSlThreads / 64) * (64 / G)));
 #define D4W_SL_LAUNCH(GG, TT, AA)                                                                                            \
     do {                                                                                                                     \
@@ -1028,6 +1032,7 @@ int d4w_sosfiltfilt_f32(const float* x, float* y, int nx, int ns, const double* 
         const SlRows xr{x, (size_t)ns, 0, nx}, tr{t, (size_t)ns, 0, nx}, yr{y, (size_t)ns, 0, nx}, pr{first, 1, 0, nx};
         return sos_lanes_both(nsec, precise, A, Ad, xr, tr, yr, 0, ns, 0, ns, edge, nx, ns, padlen, pr, (float)dcg2, stream);
     }
+    g_sos_last_form = 1 + (precise ? 800 : 400);
     if (precise) {
         int rcd = sos_launch<false, double>(nsec, grid, stream, Ad, x, nullptr, t, edge, nx, ns, padlen, S, W, first, 0.f);
         if (rcd) return rcd;
@@ -1037,6 +1042,8 @@ int d4w_sosfiltfilt_f32(const float* x, float* y, int nx, int ns, const double* 
     if (rc) return rc;
     return sos_launch<true, float>(nsec, grid, stream, A, t, edge, y, nullptr, nx, ns, padlen, S, W, first, (float)dcg2);
 }
+
+int d4w_sosfiltfilt_last_form(void) { return g_sos_last_form; }
 
 size_t d4w_sosfiltfilt_ends_ws_bytes(int nx, int piece, int padlen) {
     if (nx < 1 || piece < 1 || padlen < 0) return 0;

@@ -230,6 +230,11 @@ size_t d4w_sosfiltfilt_ws_bytes(int nx, int ns, int padlen);
 int d4w_sosfiltfilt_f32(const float* x, float* y, int nx, int ns, const double* sos_host,
                         const double* zi_host, int nsec, int padlen, int seg_len, int warm,
                         void* ws, void* stream);
+/* What the calling thread's last successful d4w_sosfiltfilt_f32 / d4w_sosfiltfilt_ends*_f32 call dispatched (0 before the
+ * first): lanes per row + 100 x bytes per state -- 1 = one row per lane (sos_pass), 8 or 16 = the sections of a row
+ * on that many adjacent lanes (sos_pass_lanes); 400 = float states, 800 = double states (chosen from the design's conditioning
+ * or by D4W_SOS_F64).  E.g. 408, 816, 401, 801.  Host bookkeeping only: for tests and diagnostics. */
+int d4w_sosfiltfilt_last_form(void);
 /* The two row-end pieces of every row filtered exactly and written into y -- what the overlap-save form of the band-pass
  * (d4w_fir_fft_f32: the interior) leaves to the recursion: the left piece x[r][0 .. piece) and the right piece
  * x[r][ns - piece .. ns) of every row run d4w_sosfiltfilt_f32's arithmetic as rows of `piece` samples (filtfilt's edge rule at

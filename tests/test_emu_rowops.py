@@ -7,6 +7,7 @@ import pytest
 import scipy.signal as sps
 
 from oracle import d4w_oracle as orc
+from tests import sos_cases as sc
 from tests.emu_util import load_emu, vp
 
 TOL = 1e-5
@@ -776,3 +777,55 @@ def test_row_end_pieces_in_place(emu, phases):
         mask[sl] = False
         assert np.all(y1[:, mask] == 7.5)
     assert emu.d4w_sosfiltfilt_ends_sides_f32(vp(x), vp(y), nx, ns, vp(sos), vp(zi), sos.shape[0], padlen, piece, keep, 0, 4, vp(ws), None) != 0
+
+
+# ------------------------------------------------------------------------------------------
+# the zero-phase filter's table (tests/sos_cases.py): emulator twins of tests/test_sos_paths_gpu.py
+# ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sc.NAMES)
+def test_sos_table_lanes_kernel(emu, name):
+    """sos_pass_lanes on every design of the table -- 1 to 10 sections, G = 8 and G = 16, float and double states -- at one
+    ragged shape (37 rows: ragged lanes, waves and workgroups for 8 and 4 rows per wave; 333 samples: several 64-sample
+    chunks, ragged), all input kinds, against float64 at 1e-5 of the block (offset-heavy low-pass rows: sos_cases.judge)."""
+    x, ref, kinds, padlen = sc.case(name, 37, 333)
+    sc.judge(sosfiltfilt_emu(emu, x, sc.design(name), padlen), ref, kinds, name)
+    assert emu.d4w_sosfiltfilt_last_form() == sc.expected_form(name)
+
+
+@pytest.mark.parametrize("name", sc.NAMES)
+def test_sos_table_segmented_kernel(emu, name):
+    """sos_pass<N> on every design of the table (N = 1 .. 10, both precisions): warm-started segments, at least three per
+    row, a row length that is no multiple of the 32-sample chunk, five rows of a 64-row wave."""
+    from das4whales_amd.dsp import _sos_decay_samples_uncached
+    sos = sc.design(name)
+    seg_len, warm, ns = sc.segmentation(sos, _sos_decay_samples_uncached(sos))
+    x, ref, kinds, padlen = sc.case(name, 5 if "lp" not in name else 6, ns)
+    sc.judge(sosfiltfilt_emu(emu, x, sos, padlen, seg_len=seg_len, warm=warm), ref, kinds, name)
+    assert emu.d4w_sosfiltfilt_last_form() == sc.expected_form(name, lanes=False)
+
+
+@pytest.mark.parametrize("name", ["lp17", "bp10w"])
+def test_sos_table_row_end_pieces(emu, name):
+    """The row-end pieces of a design other than the 14-30 Hz band-pass -- lp17: 9 sections on 16 lanes, DC gain 1, rows whose
+    offset is 1e3 and 1e5 x the signal; bp10w: double states -- with the piece and keep lengths the overlap-save form uses
+    (P = 2 E, E): phases as two calls, both sides and each side alone, against float64 (sos_cases.check_row_ends)."""
+    from das4whales_amd.dsp import _zero_phase_response
+    sos = sc.design(name)
+    padlen = sc.default_padlen(sos)
+    _, K, E = _zero_phase_response(sos, tol_taps=1e-7, tol_edge=1e-8)
+    P, nx = 2 * E, 9
+    ns = 4 * P + 3
+    x = np.ascontiguousarray(sc.rows(name, nx, ns))
+    zi = np.ascontiguousarray(sps.sosfilt_zi(sos))
+    emu.d4w_sosfiltfilt_ends_ws_bytes.restype = ctypes.c_size_t
+    ws = np.empty(emu.d4w_sosfiltfilt_ends_ws_bytes(nx, P, padlen), dtype=np.uint8)
+
+    def run(phases, sides):
+        y = np.full_like(x, 7.5)
+        for ph in phases:
+            rc = emu.d4w_sosfiltfilt_ends_sides_f32(vp(x), vp(y), nx, ns, vp(sos), vp(zi), sos.shape[0], padlen, P, E, ph, sides,
+                                                    vp(ws), None) if sides != 3 else \
+                emu.d4w_sosfiltfilt_ends_f32(vp(x), vp(y), nx, ns, vp(sos), vp(zi), sos.shape[0], padlen, P, E, ph, vp(ws), None)
+            assert rc == 0, emu.d4w_last_error()
+        return y
+    sc.check_row_ends(run, name, x, sc.row_kinds(name, nx), padlen, P, E)
