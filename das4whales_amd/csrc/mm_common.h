@@ -24,6 +24,7 @@ __device__ __forceinline__ mm_f4 mm_mfma(const mm_h8& a, const mm_h8& b, mm_f4 c
 __device__ __forceinline__ float mm_get(const mm_f4& c, int r) { return c.v[r]; }
 __device__ __forceinline__ void mm_set(mm_h8& a, int j, mm_half h) { a.v[j] = h; }
 __device__ __forceinline__ int mm_uniform(int v) { return v; }
+__device__ __forceinline__ float mm_uniform(float v) { return v; }
 __device__ __forceinline__ void mm_sched_fence() {}
 __device__ __forceinline__ void mm_store4(float* p, float a, float b, float c, float d) { p[0] = a; p[1] = b; p[2] = c; p[3] = d; }
 __device__ __forceinline__ void mm_store1(float* p, float v) { *p = v; }
@@ -45,6 +46,8 @@ __device__ __forceinline__ mm_f4 mm_mfma(mm_h8 a, mm_h8 b, mm_f4 c) { return __b
 __device__ __forceinline__ float mm_get(const mm_f4& c, int r) { return c[r]; }
 __device__ __forceinline__ void mm_set(mm_h8& a, int j, mm_half h) { a[j] = h; }
 __device__ __forceinline__ int mm_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// (a float every lane of the wave holds alike, moved to a scalar register)
+__device__ __forceinline__ float mm_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 __device__ __forceinline__ void mm_sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 __device__ __forceinline__ void mm_store4(float* p, float a, float b, float c, float d) {
     mm_f4 t = {a, b, c, d};

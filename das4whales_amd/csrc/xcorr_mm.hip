@@ -26,7 +26,8 @@
 // nothing overflows binary16; small values use its subnormals, which the conversions and the matrix instruction keep.  Measured against a float64 correlation the result is as close as the float32
 // FFT kernel's (tests/test_rowops_gpu.py).
 //
-// Launch shape.  Persistent workgroups (256 threads, 4 waves) walk chunks of 4096 lags of one row; the chunk's
+// Launch shape.  Persistent workgroups (256 threads, 4 waves) walk chunks of 4096 lags of one row (8192 where two templates
+// share the launch: two groups of 4096, each staged with its own halo, scale and prefix carry -- MmGeom); the chunk's
 // 4096 + 192 samples are loaded one chunk AHEAD into registers (17 floats per lane), converted and written to
 // one of two LDS buffers (hi / lo arrays in sample order: the four lane groups of a fragment read hit 16 different
 // 16-byte slots each), ONE barrier per chunk, then every wave runs four 16 x 16 tiles (256 lags each,
@@ -42,7 +43,10 @@ namespace d4w {
 #ifndef D4W_MM_CH
 #define D4W_MM_CH 4096
 #endif
-constexpr int kMmCH = D4W_MM_CH;                 // lags per chunk (8192 measured: see DESIGN 3.3)
+constexpr int kMmCH = D4W_MM_CH;                 // lags per chunk of the one-template kernels
+constexpr int kMmCHPair = 8192;                  // ... of the two-template kernels (0.22 ms faster there, 2.4 ms slower for one template: DESIGN 3.3)
+constexpr int kMmGroup = 4096;                   // a longer chunk is staged, scaled and prefix-summed in GROUPS of this many lags: the arithmetic of a lag
+                                                 // does not depend on the chunk length its kernel walks the row in
 constexpr int kMmKS = 6;                         // k-steps of 32 of the two-template kernels -> Toeplitz depth 192, supports <= 177
 constexpr int kMmKSLong = 8;                     // ... of the one-template kernel for longer supports: depth 256, supports <= 241
 constexpr int kMmKSMax = 16;                     // deepest one-template kernel: depth 512, a SECTION of <= 497 taps (128 VGPRs of fragments)
@@ -50,14 +54,27 @@ constexpr int kMmSection = 32 * kMmKSMax - 16;   // taps per section of a longer
 constexpr int kMmMaxSupport = 32 * kMmKSLong - 15;
 constexpr int kMmMaxSections = 16;               // templates of up to 16 x 496 taps run section by section (one accumulate launch each)
 constexpr int kMmThreads = 256;
-// geometry of a chunk for a Toeplitz depth of KSM k-steps
-template <int KSM>
+// geometry of a chunk of CH lags for a Toeplitz depth of KSM k-steps
+template <int KSM, int CH = kMmCH>
 struct MmGeom {
+    static constexpr int G = CH > kMmGroup ? CH / kMmGroup : 1;  // groups per chunk
+    static constexpr int GL = CH / G;                            // lags per group
     static constexpr int Halo = 32 * KSM;                        // samples staged beyond the chunk
-    static constexpr int Stage = kMmCH + Halo;                   // samples per chunk (4288 at KSM = 6)
+    static constexpr int Stage = CH + Halo;                      // samples loaded per chunk (4288 at KSM = 6 and 4096 lags)
     static constexpr int Q = (Stage + 4 * kMmThreads - 1) / (4 * kMmThreads);      // 16-byte loads per lane: 5
     static constexpr int LastQ = (Stage - (Q - 1) * 4 * kMmThreads) / 4;         // lanes that take the last load (48 at KSM = 6)
-    static constexpr int Arr = Stage + 8;                        // halves per LDS array
+    static constexpr int GStage = GL + Halo;                     // halves a group takes in an LDS array: its lags and ITS OWN halo (the
+                                                                 //   first Halo samples of the next group once more, in this group's scale)
+    static constexpr int Arr = G * GStage + 8;                   // halves per LDS array
+    static constexpr int QG = GL / (4 * kMmThreads);             // loads per lane and group
+    static constexpr int Blk = CH / 4;                           // lanes x loads of a chunk's own samples: one prefix each
+    // TAIL: floats of the block-prefix table per buffer.  Every fourth lane's prefix is a block of 16's, the only ones read; one
+    // group keeps the table of all lanes (no predicated store), a longer chunk the quarter that is read (LDS: two workgroups per CU)
+    static constexpr int Pb = G == 1 ? Blk : Blk / 4;
+    static constexpr size_t lds_bytes(bool tail) {
+        return (size_t)4 * Arr * sizeof(mm_half) + 8 * G * sizeof(float) + (tail ? ((size_t)2 * Pb + 2 * 16 * G) * sizeof(float) : 0);
+    }
+    static_assert(CH % (4 * kMmThreads) == 0 && GL % (4 * kMmThreads) == 0 && Halo <= 4 * kMmThreads, "a group is whole loads; its halo lies in one");
 };
 // LDS index of sample h of the chunk: the plain order.  ds_read_b128 is served in four NON-contiguous 16-lane groups
 // ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ...: MI355X_MICROARCH.md, LDS), and with lane (a, g) reading the 16-byte
@@ -139,31 +156,26 @@ __device__ __forceinline__ float mm_wave_scan(float v) {
 // loses on: 6.32 against 6.11 ms for the kernel where every wave runs both templates (profiles/r06m/mm_wave_split.txt).
 // Instantiated as <KS, 0, 3, ., ., true>: the one-template code with the template, output, tail coefficient and row maxima
 // chosen by the wave.
-template <int KS0, int KS1, int WPS, bool TAIL = false, bool WMAX = false, bool WSPLIT = false>
+template <int KS0, int KS1, int WPS, bool TAIL = false, bool WMAX = false, bool WSPLIT = false, int CH = kMmCH>
 __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
     static_assert(!(WSPLIT && KS1 > 0), "the wave-split kernel is the one-template code run by two wave pairs");
     constexpr int KSM = KS0 > KS1 ? KS0 : KS1;
-    using GEO = MmGeom<KSM>;
+    using GEO = MmGeom<KSM, CH>;
     constexpr int kMmHalo = GEO::Halo, kMmStage = GEO::Stage, kMmQ = GEO::Q, kMmLastQ = GEO::LastQ, kMmArr = GEO::Arr;
-    constexpr int kSeg = 4 * kMmQ;                                  // 256-thread segments of a stage (1024 samples each), <= 20
+    // CH lags per chunk = G groups of GL: one barrier, one set of loads and one round of bookkeeping per CHUNK; one scale, one LDS
+    // stage with its own halo and one prefix carry per GROUP -- what a lag is computed from is the same for every CH
+    constexpr int G = GEO::G, GL = GEO::GL, QG = GEO::QG, kPb = GEO::Pb;
     D4W_DYN_LDS(smem_raw);
     mm_half* lds = reinterpret_cast<mm_half*>(smem_raw);           // [2 buffers][hi | lo][kMmArr]
-    float* red = reinterpret_cast<float*>(lds + 4 * kMmArr);       // [2][4] chunk maxima of the waves
-    constexpr int kBlk = kMmCH / 4;                                 // lanes x loads of a chunk's own samples (1024): one prefix each, every fourth one is a block of 16's
-    float* pb = red + 8;                                            // TAIL: [2][kBlk] prefix before each lane's four samples, inside its wave's segment
-    float* wt = pb + 2 * kBlk;                                      // TAIL: [2][16] the segments' totals (a segment = 256 samples = one wave's share of 1024)
+    float* red = reinterpret_cast<float*>(lds + 4 * kMmArr);       // [2][G][4] group maxima of the waves
+    float* pb = red + 8 * G;                                        // TAIL: [2][kPb] prefix before a lane's four samples, inside its wave's segment
+    float* wt = pb + 2 * kPb;                                       // TAIL: [2][16 G] the segments' totals (a segment = 256 samples = one wave's share of 1024)
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63, wv = mm_uniform(tid >> 6);
     const int n16 = lane & 15, g = lane >> 4;
     const int ns = P.ns;
     const int tsel = WSPLIT ? (wv >> 1) : 0;                        // WSPLIT: the template this wave runs (wave-uniform)
 
-    // ---- the chunks of this workgroup: XCD j (workgroup id mod 8) owns the contiguous range [j T / 8, (j + 1) T / 8)
-    const int nchunk = (ns + kMmCH - 1) / kMmCH;
-    const long long total = (long long)P.nx * nchunk;
-    const int nparts = min(8, (int)gridDim.x);
-    const int xcd = (int)blockIdx.x % nparts, wq = (int)blockIdx.x / nparts, nq = ((int)gridDim.x - xcd + nparts - 1) / nparts;
-    const long long lo_c = total * xcd / nparts, hi_c = total * (xcd + 1) / nparts;
     // ---- the templates' Toeplitz fragments: A_t[kk][i = n16][u = 32 kk + 8 g + j] = t[u - i] / ts_t, split hi / lo
     mm_h8 a0h[KS0], a0l[KS0];
     mm_h8 a1h[KS1 ? KS1 : 1], a1l[KS1 ? KS1 : 1];
@@ -174,16 +186,42 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
 #else
     constexpr bool kRows = TAIL;
 #endif
-    auto next_chunk = [&](long long c) -> long long {
+    // ---- the chunks of this workgroup, walked as (row, chunk inside the row): wave-uniform integers moved on by additions and
+    // one compare per chunk -- every division is here, ahead of the loop
+    const int nchunk = (ns + CH - 1) / CH;
+    int row_n = 0, cin_n = 0;                                       // the chunk being loaded ...
+    size_t roff_n = 0;                                              // ... and its row's first sample in x / y0 / y1
+    bool more_n = false;                                            // there is one
+    int left_n = 0, d_row = 0, d_cin = 0;                           // dealt chunks: how many are left; the step of nq chunks as rows + chunks
+    if constexpr (kRows) {
+        row_n = (int)blockIdx.x;
+        more_n = row_n < P.nx;
+    } else {
+        // XCD j (workgroup id mod 8) owns the contiguous range [j T / 8, (j + 1) T / 8) of the T chunks
+        const long long total = (long long)P.nx * nchunk;
+        const int nparts = min(8, (int)gridDim.x);
+        const int xcd = (int)blockIdx.x % nparts, wq = (int)blockIdx.x / nparts, nq = ((int)gridDim.x - xcd + nparts - 1) / nparts;
+        const long long lo_c = total * xcd / nparts, hi_c = total * (xcd + 1) / nparts;
+        const long long c_first = lo_c + wq;
+        left_n = c_first < hi_c ? (int)((hi_c - c_first + nq - 1) / nq) : 0;
+        row_n = (int)(c_first / nchunk);
+        cin_n = (int)(c_first - (long long)row_n * nchunk);
+        d_row = nq / nchunk;
+        d_cin = nq - d_row * nchunk;
+        more_n = left_n > 0;
+    }
+    roff_n = (size_t)row_n * ns;
+    const size_t d_off = (size_t)(kRows ? (int)gridDim.x : d_row) * ns;
+    auto advance = [&]() {                                          // (row_n, cin_n) -> the workgroup's next chunk
         if constexpr (kRows) {
-            const long long r = c / nchunk;
-            return (c - r * nchunk + 1 < nchunk) ? c + 1 : (r + (long long)gridDim.x) * nchunk;
+            if (++cin_n == nchunk) { cin_n = 0; row_n += (int)gridDim.x; roff_n += d_off; }
+            more_n = row_n < P.nx;
         } else {
-            return c + nq;
+            cin_n += d_cin; row_n += d_row; roff_n += d_off;
+            if (cin_n >= nchunk) { cin_n -= nchunk; ++row_n; roff_n += (size_t)ns; }
+            more_n = --left_n > 0;
         }
     };
-    const long long end_c = kRows ? total : hi_c;
-    long long c_n = kRows ? (long long)blockIdx.x * nchunk : lo_c + wq;
     {
         // taps -> LDS first (zero outside the support), so that the 8 x KS fragment values of a lane are LDS reads
         float* tl = reinterpret_cast<float*>(smem_raw);              // [2][16 + kMmHalo] before the row buffers are in use
@@ -227,25 +265,26 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
     float4 pre[kMmQ];                                               // the chunk being loaded (raw samples)
     Mean2 mu_n{0.f, 0.f};                                           // its row's mean (hi + lo) ...
     float g_n = 1.f;                                                // ... and 1 / maxabs
-    bool heavy_n = false;                                           // the row is (nearly) all offset: scale it chunk by chunk
+    bool heavy_n = false;                                           // the row is (nearly) all offset: scale it group by group
     bool tail_n = false;                                            // the chunk reaches beyond the row (wave-uniform)
-    int row_n = 0, c0_n = 0;
+    int c0_n = 0;
 
-    auto issue = [&](long long c) {                                 // global loads of chunk c into pre[]
-        row_n = (int)(c / nchunk);
-        c0_n = (int)(c - (long long)row_n * nchunk) * kMmCH;
-        mu_n = mean2_load(P.mean, row_n);
-        g_n = 1.f;
+    auto issue = [&]() {                                            // global loads of chunk (row_n, cin_n) into pre[]
+        c0_n = cin_n * CH;
+        if (!kRows || cin_n == 0) {                                 // the row's statistics: once per row where a workgroup walks whole rows
+            mu_n = mean2_load(P.mean, row_n);
+            g_n = 1.f;
+            if (P.maxabs) {
+                const float a = P.maxabs[row_n];
+                g_n = (a > 0.f) ? 1.0f / a : 0.f;
+                // |mean| within 1 / 128 of max|x|: the deviations are at most a hundredth of what 1 / max|x| normalises by and
+                // would sit in (or below) binary16's subnormal range -- such rows take the per-group power of two as well
+                heavy_n = fabsf(mu_n.hi) > 0.9921875f * a;
+            }
+        }
         const int s0 = c0_n + P.shift;                              // first sample of the chunk's stage
         tail_n = s0 + kMmStage > ns;
-        if (P.maxabs) {
-            const float a = P.maxabs[row_n];
-            g_n = (a > 0.f) ? 1.0f / a : 0.f;
-            // |mean| within 1 / 128 of max|x|: the deviations are at most a hundredth of what 1 / max|x| normalises by and
-            // would sit in (or below) binary16's subnormal range -- such rows take the per-chunk power of two as well
-            heavy_n = fabsf(mu_n.hi) > 0.9921875f * a;
-        }
-        const float* xr = P.x + (size_t)row_n * ns;
+        const float* xr = P.x + roff_n;
         const bool al = (reinterpret_cast<uintptr_t>(xr + s0) & 15) == 0;
         if (al && s0 + kMmStage <= ns) {
             const float4* p = reinterpret_cast<const float4*>(xr + s0) + tid;
@@ -295,34 +334,37 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
         }
     };
 
-    if (c_n < end_c) issue(c_n);
+    if (more_n) issue();
     int buf = 0;
     constexpr bool want_max = WMAX;
     // TAIL: prefix of the normalised row at the chunk's first sample, a float64 kept as two wave-uniform floats (scalar registers)
     float pst_hi = 0.f, pst_lo = 0.f;
-    for (long long c = c_n; c < end_c;) {
-        const int row = row_n, c0 = c0_n;
+    for (bool more = more_n; more; more = more_n) {
+        const int row = row_n, c0 = c0_n, cin = cin_n;             // the chunk to compute: its row, first lag, number inside the row
+        const size_t roff = roff_n;
         const Mean2 mu = mu_n;
         const bool tail = tail_n;
         const int n_valid = ns + ((P.xnext && P.n_next > 0) ? P.n_next : 0) - c0 - P.shift;     // samples of the stage that exist
-        float gsc = g_n, osx = 1.f;                                 // x scale applied before the split, and what undoes it
-        const float gout = g_n;                                     // the normalisation's factor, applied to the outputs when a chunk scales itself
+        const float gout = g_n;                                     // the normalisation's factor, applied to the outputs when a group scales itself
         const bool own_scale = !P.maxabs || heavy_n;                // wave- and workgroup-uniform (one row per chunk)
+        float gsc[G], osx[G];                                       // per group: x scale applied before the split, and what undoes it
+        static_for<G>([&](auto gg) { gsc[decltype(gg)::value] = g_n; osx[decltype(gg)::value] = 1.f; });
         mm_half* bh = lds + (size_t)buf * 2 * kMmArr;
         mm_half* bl = bh + kMmArr;
-        const long long c_next = next_chunk(c);
-        const int cin = c0 / kMmCH;                                 // the chunk's number inside its row
+        advance();
         if (TAIL && cin == 0) { pst_hi = 0.f; pst_lo = 0.f; }
-        const float pst = pst_hi;
+        // load q of a lane lies in group q / QG (the chunk's own halo, the last load, in the last group); the first load of a
+        // later group holds, in its first kMmHalo / 4 lanes, the halo of the group before as well
         // ---- convert the loaded chunk: (x - mu) * scale -> hi / lo halves in LDS
         if (own_scale) {
-            // no row maximum from the caller, or a row that is all offset: this chunk's own power of two.  (With a row maximum the rows are scaled by
+            // no row maximum from the caller, or a row that is all offset: the group's own power of two.  (With a row maximum the rows are scaled by
             // 1 / max|x| alone: a row whose signal is small against its offset then sits low in the binary16 range, which is
             // harmless -- v_cvt_f16_f32 and the matrix instruction keep binary16 subnormals, scripts/probe/denorm_probe.py:
             // taps at 1e-7 of the largest one still come out at 3e-7 -- and the per-chunk reduction costs a barrier, 3 %.)
-            float m = 0.f;
+            float m[G];
+            static_for<G>([&](auto gg) { m[decltype(gg)::value] = 0.f; });
             static_for<kMmQ>([&](auto qq) {
-                constexpr int q = decltype(qq)::value;
+                constexpr int q = decltype(qq)::value, gq = q / QG < G ? q / QG : G - 1;
                 if (q < kMmQ - 1 || tid < kMmLastQ) {
                     const float4 v = pre[q];
                     const int at = 4 * (tid + q * kMmThreads);
@@ -333,83 +375,122 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
                         if (at + 2 >= n_valid) d2 = 0.f;
                         if (at + 3 >= n_valid) d3 = 0.f;
                     }
-                    m = fmaxf(fmaxf(m, fmaxf(fabsf(d0), fabsf(d1))), fmaxf(fabsf(d2), fabsf(d3)));
+                    m[gq] = fmaxf(fmaxf(m[gq], fmaxf(fabsf(d0), fabsf(d1))), fmaxf(fabsf(d2), fabsf(d3)));
+                    if constexpr (q >= QG && q < G * QG && q % QG == 0) {
+                        if (tid < kMmHalo / 4) m[gq - 1] = fmaxf(fmaxf(m[gq - 1], fmaxf(fabsf(d0), fabsf(d1))), fmaxf(fabsf(d2), fabsf(d3)));
+                    }
                 }
             });
-            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-            if (lane == 0) red[wv + 4 * buf] = m;
+            static_for<G>([&](auto gg) {
+                constexpr int gi = decltype(gg)::value;
+                for (int o = 32; o > 0; o >>= 1) m[gi] = fmaxf(m[gi], __shfl_xor(m[gi], o));
+                if (lane == 0) red[wv + 4 * (gi + G * buf)] = m[gi];
+            });
             lds_barrier();
-            m = fmaxf(fmaxf(red[4 * buf], red[4 * buf + 1]), fmaxf(red[4 * buf + 2], red[4 * buf + 3]));
-            mm_pow2_scale(m, osx, gsc);
+            static_for<G>([&](auto gg) {
+                constexpr int gi = decltype(gg)::value;
+                const float* r4 = red + 4 * (gi + G * buf);
+                float up, down;
+                mm_pow2_scale(fmaxf(fmaxf(r4[0], r4[1]), fmaxf(r4[2], r4[3])), up, down);
+                osx[gi] = mm_uniform(up);                          // (every lane read the same four words: scalar registers from here on)
+                gsc[gi] = mm_uniform(down);
+            });
         }
-        const float mlg = -mu.lo * gsc;
+        // one lane's four samples of load q, scaled for group gi
+        auto scaled = [&](const float4 v, int at, auto gg, float (&s)[4]) {
+            constexpr int gi = decltype(gg)::value;
+            const float mlg = -mu.lo * gsc[gi];
+            // ((x - hi) - lo) g as (x - hi) g - lo g: the two-float mean at the instruction count of a float32 one (x - hi is
+            // exact where the offset dominates, the product is rounded once)
+#ifdef D4W_MM_V_FLOATMEAN          // (probe builds: what the two-float mean costs)
+            s[0] = (v.x - mu.hi) * gsc[gi]; s[1] = (v.y - mu.hi) * gsc[gi]; s[2] = (v.z - mu.hi) * gsc[gi]; s[3] = (v.w - mu.hi) * gsc[gi];
+#else
+            s[0] = fmaf(v.x - mu.hi, gsc[gi], mlg); s[1] = fmaf(v.y - mu.hi, gsc[gi], mlg); s[2] = fmaf(v.z - mu.hi, gsc[gi], mlg); s[3] = fmaf(v.w - mu.hi, gsc[gi], mlg);
+#endif
+            // the next file's head (or statistics that are not the rows' own, D4W_MM_CLAMP=1) may leave |v| beyond binary16's
+            // range: inf - inf would turn a whole tile into NaN where the float32 forms stay finite; one v_med3_f32 per
+            // sample, only where asked for (a kernel argument: a scalar branch)
+            if (P.clamp && !own_scale) static_for<4>([&](auto ee) { constexpr int e = decltype(ee)::value; s[e] = mm_clamp_half(s[e]); });
+            if (tail) {                                              // beyond the data: the zero padding of the correlation
+                static_for<4>([&](auto ee) { constexpr int e = decltype(ee)::value; if (at + e >= n_valid) s[e] = 0.f; });
+            }
+        };
         static_for<kMmQ>([&](auto qq) {
-            constexpr int q = decltype(qq)::value;
+            constexpr int q = decltype(qq)::value, gq = q / QG < G ? q / QG : G - 1;
             float s[4] = {0.f, 0.f, 0.f, 0.f};
             const bool mine = q < kMmQ - 1 || tid < kMmLastQ;
-            const int at = mm_pidx(4 * (tid + q * kMmThreads));
-            if (mine) {
-                const float4 v = pre[q];
-                // ((x - hi) - lo) g as (x - hi) g - lo g: the two-float mean at the instruction count of a float32 one (x - hi is
-                // exact where the offset dominates, the product is rounded once)
-#ifdef D4W_MM_V_FLOATMEAN          // (probe builds: what the two-float mean costs)
-                s[0] = (v.x - mu.hi) * gsc; s[1] = (v.y - mu.hi) * gsc; s[2] = (v.z - mu.hi) * gsc; s[3] = (v.w - mu.hi) * gsc;
+            const int at = 4 * (tid + q * kMmThreads);              // the lane's first sample inside the chunk
+#ifdef D4W_MM_V_NOCONV              // (probe builds: loads awaited, nothing converted or written to LDS -- WRONG values, timing only)
+            if (mine && pre[q].x == 1.2345e30f) {
 #else
-                s[0] = fmaf(v.x - mu.hi, gsc, mlg); s[1] = fmaf(v.y - mu.hi, gsc, mlg); s[2] = fmaf(v.z - mu.hi, gsc, mlg); s[3] = fmaf(v.w - mu.hi, gsc, mlg);
+            if (mine) {
 #endif
-                // the next file's head (or statistics that are not the rows' own, D4W_MM_CLAMP=1) may leave |v| beyond binary16's
-                // range: inf - inf would turn a whole tile into NaN where the float32 forms stay finite; one v_med3_f32 per
-                // sample, only where asked for (a kernel argument: a scalar branch)
-                if (P.clamp && !own_scale) static_for<4>([&](auto ee) { constexpr int e = decltype(ee)::value; s[e] = mm_clamp_half(s[e]); });
-                if (tail) {                                          // beyond the data: the zero padding of the correlation
-                    const int a0 = 4 * (tid + q * kMmThreads);
-                    static_for<4>([&](auto ee) { constexpr int e = decltype(ee)::value; if (a0 + e >= n_valid) s[e] = 0.f; });
-                }
+                scaled(pre[q], at, std::integral_constant<int, gq>{}, s);
+                // group gq's stage starts at gq (GL + halo) in the arrays: sample `at` of the chunk sits gq halos further on
 #ifdef D4W_MM_V_OLDSPLIT
                 mm_half h[4], l[4];
                 static_for<4>([&](auto ee) { constexpr int e = decltype(ee)::value; mm_split(s[e], h[e], l[e]); });
-                mm_put4(bh + at, h);
-                mm_put4(bl + at, l);
+                mm_put4(bh + mm_pidx(at + gq * kMmHalo), h);
+                mm_put4(bl + mm_pidx(at + gq * kMmHalo), l);
 #else
-                mm_split_put4(s, bh + at, bl + at);
+                mm_split_put4(s, bh + mm_pidx(at + gq * kMmHalo), bl + mm_pidx(at + gq * kMmHalo));
 #endif
+                if constexpr (q >= QG && q < G * QG && q % QG == 0) {              // ... and once more as the halo of the group before, in that group's scale
+                    if (tid < kMmHalo / 4) {
+                        float h4[4];
+                        scaled(pre[q], at, std::integral_constant<int, gq - 1>{}, h4);
+                        mm_split_put4(h4, bh + mm_pidx(at + (gq - 1) * kMmHalo), bl + mm_pidx(at + (gq - 1) * kMmHalo));
+                    }
+                }
             }
 #ifdef D4W_MM_V_TAIL_NOSCAN         // (probe builds: no prefix scan, no tail term -- timing only)
             if constexpr (false) {
 #else
-            if constexpr (TAIL && q < kMmCH / (4 * kMmThreads)) {   // the chunk's own 4096 samples (the halo adds no block of lags)
+            if constexpr (TAIL && q < G * QG) {                     // the chunk's own samples (the halo adds no block of lags)
 #endif
                 // prefix of the scaled samples at every fourth lane = every block of 16 samples, inside this wave's segment
                 const float t4 = (s[0] + s[1]) + (s[2] + s[3]);
                 const float inc = mm_wave_scan(t4);
-                pb[buf * kBlk + kMmThreads * q + tid] = inc - t4;        // (every lane stores: no exec-mask juggling; the epilogue reads every fourth)
-                if (lane == 63) wt[buf * 16 + 4 * q + wv] = inc;
+                if constexpr (G == 1) pb[buf * kPb + kMmThreads * q + tid] = inc - t4;     // (every lane stores: no exec-mask juggling; the epilogue reads every fourth)
+                else if ((lane & 3) == 0) pb[buf * kPb + (kMmThreads / 4) * q + (tid >> 2)] = inc - t4;
+                if (lane == 63) wt[buf * 16 * G + 4 * q + wv] = inc;
             }
         });
         // ---- next chunk's loads fly across the barrier and the matrix phase
-        if (c_next < end_c) issue(c_next);
+        if (more_n) issue();
         lds_barrier();
-        // ---- 16 tiles of 256 lags, 4 per wave: C[i][a] (+)= A[i][u] B[u][a]
-        float* ya = ((WSPLIT && tsel) ? P.y1 : P.y0) + (size_t)row * ns;
-        float* yb = KS1 ? P.y1 + (size_t)row * ns : nullptr;
+        // ---- CH / 256 tiles of 256 lags, a quarter per wave: C[i][a] (+)= A[i][u] B[u][a]
+        float* ya = ((WSPLIT && tsel) ? P.y1 : P.y0) + roff;
+        float* yb = KS1 ? P.y1 + roff : nullptr;
         const bool valign = ((reinterpret_cast<uintptr_t>(ya + c0) & 15) == 0) && (!KS1 || (reinterpret_cast<uintptr_t>(yb + c0) & 15) == 0);
-        const float oxs = (own_scale && P.maxabs) ? osx * gout : osx;
-        const float o0 = osc0 * oxs, o1 = osc1 * oxs;
-        float segoff = 0.f;                                         // TAIL: the prefix at each segment's start (lane l: segment l), formed at the first tile's end
-        // the wave's four tiles as ONE software pipeline over (tile, k-step): the fragment pair of step s + PF is requested
+        float oxs[G], o0[G], o1[G];
+        static_for<G>([&](auto gg) {
+            constexpr int gi = decltype(gg)::value;
+            oxs[gi] = (own_scale && P.maxabs) ? osx[gi] * gout : osx[gi];
+            o0[gi] = osc0 * oxs[gi];
+            o1[gi] = osc1 * oxs[gi];
+        });
+        // TAIL, per group: the prefix at each segment's start (lane l: segment l) and the row's prefix at the group's first sample,
+        // formed at the first tile's end
+        float segoff[G], pstg[G];
+        static_for<G>([&](auto gg) { segoff[decltype(gg)::value] = 0.f; pstg[decltype(gg)::value] = 0.f; });
+        // the wave's tiles as ONE software pipeline over (tile, k-step): the fragment pair of step s + PF is requested
         // before the six products of step s are issued (mm_sched_fence keeps hipcc from sinking the reads back to their use),
         // so an LDS round trip hides under 12 matrix instructions instead of stalling the wave at every k-step
-        constexpr int NTW = kMmCH / 256 / (WSPLIT ? 2 : 4), NST = NTW * KSM, PF = 2;
+        constexpr int TPW = WSPLIT ? 2 : 4;                         // a wave runs every TPW-th tile
+        constexpr int NTW = CH / 256 / TPW, NST = NTW * KSM, PF = 2;
+        constexpr int TG = GL / 256;                                // tiles per group (a multiple of TPW: the wave's ti-th tile lies in group TPW ti / TG)
         auto tile_of = [&](int ti) { return WSPLIT ? (wv & 1) + 2 * ti : wv + 4 * ti; };     // the wave's ti-th tile
-        auto frag = [&](const mm_half* arr, int T, int kk) -> mm_h8 {
-            const int gr = 32 * T + 2 * n16 + g + 4 * kk;           // 16-byte granule: sample 256 T + 16 n16 + 32 kk + 8 g
-            return *reinterpret_cast<const mm_h8*>(arr + mm_pidx(8 * gr));
+        auto frag = [&](const mm_half* arr, int ti, int kk) -> mm_h8 {
+            const int T = tile_of(ti);
+            const int gr = 32 * T + 2 * n16 + g + 4 * kk;           // 16-byte granule: sample 256 T + 16 n16 + 32 kk + 8 g of the chunk
+            return *reinterpret_cast<const mm_h8*>(arr + mm_pidx(8 * gr + (TPW * ti / TG) * kMmHalo));
         };
         mm_h8 fh[PF + 1], fl[PF + 1];
         static_for<PF>([&](auto ss) {
             constexpr int s_ = decltype(ss)::value;
-            fh[s_] = frag(bh, tile_of(s_ / KSM), s_ % KSM);
-            fl[s_] = frag(bl, tile_of(s_ / KSM), s_ % KSM);
+            fh[s_] = frag(bh, s_ / KSM, s_ % KSM);
+            fl[s_] = frag(bl, s_ / KSM, s_ % KSM);
         });
         mm_f4 c0h = mm_zero(), c0l = mm_zero(), c1h = mm_zero(), c1l = mm_zero();
         float vmax0 = -INFINITY, vmax1 = -INFINITY;                 // this lane's largest stored value of the chunk
@@ -417,11 +498,12 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
         static_for<NST>([&](auto ss) {
             constexpr int s_ = decltype(ss)::value, ti = s_ / KSM, kk = s_ % KSM;
             if constexpr (s_ + PF < NST) {
-                fh[(s_ + PF) % (PF + 1)] = frag(bh, tile_of((s_ + PF) / KSM), (s_ + PF) % KSM);
-                fl[(s_ + PF) % (PF + 1)] = frag(bl, tile_of((s_ + PF) / KSM), (s_ + PF) % KSM);
+                fh[(s_ + PF) % (PF + 1)] = frag(bh, (s_ + PF) / KSM, (s_ + PF) % KSM);
+                fl[(s_ + PF) % (PF + 1)] = frag(bl, (s_ + PF) / KSM, (s_ + PF) % KSM);
             }
             mm_sched_fence();
             const mm_h8 xh = fh[s_ % (PF + 1)], xl = fl[s_ % (PF + 1)];
+#ifndef D4W_MM_V_NOMFMA             // (probe builds without the matrix products: WRONG values, timing only)
             if constexpr (kk < KS0) {
                 c0h = mm_mfma(a0h[kk], xh, c0h);
                 c0l = mm_mfma(a0h[kk], xl, c0l);
@@ -432,33 +514,41 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             }
             if constexpr (kk < KS0) c0l = mm_mfma(a0l[kk], xh, c0l);
             if constexpr (kk < KS1) c1l = mm_mfma(a1l[kk], xh, c1l);
+#else
+            c0h[0] += (float)xh[0]; c0l[0] += (float)xl[0];
+#endif
             mm_sched_fence();
             if constexpr (kk == KSM - 1) {                          // the tile is complete: scale, combine, stream out
+                constexpr int tg = TPW * ti / TG;                   // the tile's group
                 const int T = tile_of(ti);
                 const int kl = 256 * T + 16 * n16 + 4 * g;          // this lane's four lags inside the chunk ...
                 const int k = c0 + kl;                              // ... and inside the row
                 if constexpr (ti == 0) {
                     // (here, not ahead of the matrix instructions: nothing before the first tile's end needs it)
-                // TAIL: the prefix at each segment's start (lane l: segment l) and the chunk's sum, which moves the row's prefix on (every
-                // wave forms the same values from the same LDS words)
-                if constexpr (TAIL) {
-                    const float w = lane < 16 ? wt[buf * 16 + lane] : 0.f;
-                    const float inc = mm_wave_scan(w);
-                    segoff = inc - w;
-        #ifdef D4W_EMU
-                    const float own = __shfl(inc, 15);
-        #else
-                    const float own = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inc), 15));
-        #endif
-                    const double pd = ((double)pst_hi + (double)pst_lo) + (double)(own * oxs);
-                    const float ph = (float)pd, pl2 = (float)(pd - (double)ph);
-        #ifdef D4W_EMU
-                    pst_hi = ph; pst_lo = pl2;
-        #else
-                    pst_hi = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ph)));
-                    pst_lo = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pl2)));
-        #endif
-                }
+                    // TAIL: the prefix at each segment's start (lane l: segment l of the group) and the group's sum, which moves the
+                    // row's prefix on (every wave forms the same values from the same LDS words)
+                    if constexpr (TAIL) {
+                        static_for<G>([&](auto gg) {
+                            constexpr int gi = decltype(gg)::value;
+                            const float w = lane < 16 ? wt[buf * 16 * G + 16 * gi + lane] : 0.f;
+                            const float inc = mm_wave_scan(w);
+                            segoff[gi] = inc - w;
+                            pstg[gi] = pst_hi;
+#ifdef D4W_EMU
+                            const float own = __shfl(inc, 15);
+#else
+                            const float own = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inc), 15));
+#endif
+                            const double pd = ((double)pst_hi + (double)pst_lo) + (double)(own * oxs[gi]);
+                            const float ph = (float)pd, pl2 = (float)(pd - (double)ph);
+#ifdef D4W_EMU
+                            pst_hi = ph; pst_lo = pl2;
+#else
+                            pst_hi = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ph)));
+                            pst_lo = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pl2)));
+#endif
+                        });
+                    }
                 }
                 float r0[4], r1[4];
                 float a0 = 0.f, a1 = 0.f;                           // TAIL: tail_t x (prefix at the block's first sample), the same for the lane's four lags
@@ -467,24 +557,29 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
 #else
                 if constexpr (TAIL) {
 #endif
-                    // tile T = the segment this wave converted: row prefix at the chunk + segment offset + block prefix
+                    // tile T = the segment this wave converted: row prefix at the group + segment offset + block prefix
 #ifdef D4W_EMU
-                    const float so = __shfl(segoff, T);
+                    const float so = __shfl(segoff[tg], T - tg * TG);
 #else
-                    const float so = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, segoff), T));
+                    const float so = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, segoff[tg]), T - tg * TG));
 #endif
                     // (tile T = segment T of the stage = load T / 4 of wave T % 4)
-                    const float pbk = fmaf(so + pb[buf * kBlk + kMmThreads * (T >> 2) + 64 * (T & 3) + 4 * n16], oxs, pst);
+                    const int pi = G == 1 ? kMmThreads * (T >> 2) + 64 * (T & 3) + 4 * n16 : (kMmThreads / 4) * (T >> 2) + 16 * (T & 3) + n16;
+                    const float pbk = fmaf(so + pb[buf * kPb + pi], oxs[tg], pstg[tg]);
                     a0 = ((WSPLIT && tsel) ? P.tail1 : P.tail0) * pbk;
                     a1 = P.tail1 * pbk;
                 }
                 static_for<4>([&](auto rr) {
                     constexpr int r = decltype(rr)::value;
                     // (the tail's addend rides the scaling multiply: an FMA instead of a multiply)
-                    r0[r] = fmaf(fmaf(mm_get(c0l, r), kMmLoInv, mm_get(c0h, r)), o0, a0);
-                    if constexpr (KS1 > 0) r1[r] = fmaf(fmaf(mm_get(c1l, r), kMmLoInv, mm_get(c1h, r)), o1, a1);
+                    r0[r] = fmaf(fmaf(mm_get(c0l, r), kMmLoInv, mm_get(c0h, r)), o0[tg], a0);
+                    if constexpr (KS1 > 0) r1[r] = fmaf(fmaf(mm_get(c1l, r), kMmLoInv, mm_get(c1h, r)), o1[tg], a1);
                 });
                 c0h = mm_zero(); c0l = mm_zero(); c1h = mm_zero(); c1l = mm_zero();
+#ifdef D4W_MM_V_NOSTORE             // (probe builds that write nothing: timing only)
+                if (r0[0] != 1.2345e30f) { }
+                else
+#endif
                 if (valign && k + 3 < ns) {
                     if (KS1 == 0 && P.accumulate) {                 // a later section of a long template
                         const float4 o = mm_load4_stream(reinterpret_cast<const float4*>(ya + k));
@@ -534,7 +629,6 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             }
         }
         buf ^= 1;
-        c = c_next;
     }
 }
 
@@ -549,14 +643,17 @@ int d4w_xcorr_mm_max_support(void) { return kMmSection * kMmMaxSections; }
 // one template of any support <= d4w_xcorr_mm_max_support(): sections of kMmSection taps, the first one overwriting y, the
 // later ones (x shifted by the section's first tap) accumulating into it
 // launch of xcorr_mm_rows<KS0, KS1, WPS, TAIL> with or without the row maxima
-#define D4W_MM_LAUNCH(KS0, KS1, WPS, TAIL, grid, lds, stream, Q)                                                              \
+#define D4W_MM_LAUNCH(KS0, KS1, WPS, TAIL, grid, lds, stream, Q) D4W_MM_LAUNCH_CH(KS0, KS1, WPS, TAIL, kMmCH, grid, lds, stream, Q)
+// ... walking the rows in chunks of CH lags (more than 64 KiB of LDS per workgroup has to be asked for)
+#define D4W_MM_LAUNCH_CH(KS0, KS1, WPS, TAIL, CH, grid, lds, stream, Q)                                                       \
     do {                                                                                                                      \
-        if ((Q).rowmax0) D4W_LAUNCH((xcorr_mm_rows<KS0, KS1, WPS, TAIL, true>), dim3(grid), dim3(kMmThreads), lds, stream, Q);  \
-        else D4W_LAUNCH((xcorr_mm_rows<KS0, KS1, WPS, TAIL, false>), dim3(grid), dim3(kMmThreads), lds, stream, Q);             \
+        void (*kern_)(MmArgs) = (Q).rowmax0 ? xcorr_mm_rows<KS0, KS1, WPS, TAIL, true, false, CH>                              \
+                                            : xcorr_mm_rows<KS0, KS1, WPS, TAIL, false, false, CH>;                            \
+        if ((lds) > 64 * 1024) D4W_HIP(hipFuncSetAttribute((const void*)kern_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds))); \
+        D4W_LAUNCH(kern_, dim3(grid), dim3(kMmThreads), lds, stream, Q);                                                       \
     } while (0)
 
 static int mm_one_template(MmArgs P, const float* taps, int len, float* y, float* rowmax, int grid, void* stream) {
-    auto lds_of = [](int arr) { return (size_t)4 * arr * sizeof(mm_half) + 8 * sizeof(float); };
     const int nsec = (len <= 32 * kMmKSMax - 15) ? 1 : ceil_div(len, kMmSection);
     // sections of equal length (a multiple of 16 taps, so that the shifted 16-byte loads stay aligned): 700 taps run as
     // 352 + 348 through the 12-step kernel twice instead of 496 + 204 through the 16- and the 8-step kernels
@@ -574,13 +671,13 @@ static int mm_one_template(MmArgs P, const float* taps, int len, float* y, float
         Q.rowmax1 = nullptr;
         const int ks = ceil_div(Q.len0 + 15, 32);
         if (ks <= kMmKS)
-            D4W_MM_LAUNCH(kMmKS, 0, 3, false, grid, lds_of(MmGeom<kMmKS>::Arr), stream, Q);
+            D4W_MM_LAUNCH(kMmKS, 0, 3, false, grid, MmGeom<kMmKS>::lds_bytes(false), stream, Q);
         else if (ks <= kMmKSLong)
-            D4W_MM_LAUNCH(kMmKSLong, 0, 2, false, grid, lds_of(MmGeom<kMmKSLong>::Arr), stream, Q);
+            D4W_MM_LAUNCH(kMmKSLong, 0, 2, false, grid, MmGeom<kMmKSLong>::lds_bytes(false), stream, Q);
         else if (ks <= 12)
-            D4W_MM_LAUNCH(12, 0, 2, false, grid, lds_of(MmGeom<12>::Arr), stream, Q);
+            D4W_MM_LAUNCH(12, 0, 2, false, grid, MmGeom<12>::lds_bytes(false), stream, Q);
         else
-            D4W_MM_LAUNCH(kMmKSMax, 0, 2, false, grid, lds_of(MmGeom<kMmKSMax>::Arr), stream, Q);
+            D4W_MM_LAUNCH(kMmKSMax, 0, 2, false, grid, MmGeom<kMmKSMax>::lds_bytes(false), stream, Q);
     }
     return D4W_OK;
 }
@@ -631,24 +728,22 @@ int d4w_xcorr_mm_tail_f32(const float* x, int nx, int ns, const float* xnext, in
         D4W_HIP(hipMemsetD32Async((hipDeviceptr_t)rowmax0, (int)0xFF800000u, (size_t)nx, (hipStream_t)stream));
         if (ntpl == 2) D4W_HIP(hipMemsetD32Async((hipDeviceptr_t)rowmax1, (int)0xFF800000u, (size_t)nx, (hipStream_t)stream));
     }
-    const int nchunk = ceil_div(ns, kMmCH);
-    const long long total = (long long)nx * nchunk;
-    // persistent workgroups per compute unit: 2 for two templates (207 VGPRs: the Toeplitz fragments of both templates stay
-    // in registers; a 168-register build for three workgroups spills and ran 8.5 ms against 6.6), 3 for one template
+    // persistent workgroups per compute unit: 2 for two templates (the Toeplitz fragments of both templates stay in
+    // registers; a 168-register build for three workgroups spills and ran 8.5 ms against 6.6), 3 for one template
     // (149 VGPRs), 2 for the deeper one-template kernels.  D4W_MM_WGS overrides the count (measurements).
     static const int env_wgs = [] { const char* v = getenv("D4W_MM_WGS"); const int n = v ? atoi(v) : 0; return n < 0 ? 0 : (n > 8 ? 8 : n); }();
     const int ks0 = ceil_div(len0 + 15, 32), ks1 = ceil_div(len1 + 15, 32);
     const bool fused = ntpl == 2 && std::max(ks0, ks1) <= kMmKS;
+    static const int fused_form = [] { const char* v = getenv("D4W_MM_FUSED"); return v ? atoi(v) : 2; }();
+    // the two-template kernel walks the rows in chunks of kMmCHPair lags, every other kernel in chunks of kMmCH
+    const int nchunk = ceil_div(ns, (fused && fused_form == 2) ? kMmCHPair : kMmCH);
+    const long long total = (long long)nx * nchunk;
     const int per_cu = env_wgs ? env_wgs : ((ntpl == 1 && ks0 <= kMmKS) ? 3 : 2);
     const int ncu = mm_num_cus();
     const int grid = (int)std::min<long long>(total, (long long)ncu * per_cu);
-    auto lds_of = [](int arr, bool tl) {
-        return (size_t)4 * arr * sizeof(mm_half) + 8 * sizeof(float) + (tl ? ((size_t)2 * (kMmCH / 4) + 2 * 16) * sizeof(float) : 0);
-    };
     // two templates of <= 177 samples: every wave both templates, two workgroups per CU (the kernel of rounds 4-6).  D4W_MM_FUSED=3:
     // the wave-split kernel at three workgroups per CU -- built and measured in round 6, 6.32 against 6.11 ms (with the tail 6.84
     // against 6.66): the second read of every sample fragment costs more than the third workgroup brings (profiles/r06m)
-    static const int fused_form = [] { const char* v = getenv("D4W_MM_FUSED"); return v ? atoi(v) : 2; }();
     const int per_cu_ws = env_wgs ? env_wgs : 3;
 #define D4W_MM_LAUNCH_WS(TAIL, grid, lds, Q)                                                                                            \
     do {                                                                                                                                \
@@ -659,15 +754,15 @@ int d4w_xcorr_mm_tail_f32(const float* x, int nx, int ns, const float* xnext, in
         // whole rows per workgroup (the prefix is carried along a row): at most one workgroup per row
         const int grid_t = (int)std::min<long long>((long long)nx, (long long)ncu * per_cu);
         if (fused && fused_form != 2) {
-            D4W_MM_LAUNCH_WS(true, (int)std::min<long long>((long long)nx, (long long)ncu * per_cu_ws), lds_of(MmGeom<kMmKS>::Arr, true), P);
+            D4W_MM_LAUNCH_WS(true, (int)std::min<long long>((long long)nx, (long long)ncu * per_cu_ws), MmGeom<kMmKS>::lds_bytes(true), P);
             return D4W_OK;
         }
         if (fused) {
-            const size_t lds = lds_of(MmGeom<kMmKS>::Arr, true);
+            const size_t lds = MmGeom<kMmKS, kMmCHPair>::lds_bytes(true);
             if (ks0 <= 5)
-                D4W_MM_LAUNCH(5, kMmKS, 2, true, grid_t, lds, stream, P);
+                D4W_MM_LAUNCH_CH(5, kMmKS, 2, true, kMmCHPair, grid_t, lds, stream, P);
             else
-                D4W_MM_LAUNCH(kMmKS, kMmKS, 2, true, grid_t, lds, stream, P);
+                D4W_MM_LAUNCH_CH(kMmKS, kMmKS, 2, true, kMmCHPair, grid_t, lds, stream, P);
             return D4W_OK;
         }
         for (int t = 0; t < ntpl; ++t) {
@@ -684,16 +779,16 @@ int d4w_xcorr_mm_tail_f32(const float* x, int nx, int ns, const float* xnext, in
             if (ks <= kMmKS) {
                 // (three workgroups per compute unit fit the registers only without the row maxima)
                 if (Q.rowmax0)
-                    D4W_LAUNCH((xcorr_mm_rows<kMmKS, 0, 2, true, true>), dim3(grid_t), dim3(kMmThreads), lds_of(MmGeom<kMmKS>::Arr, true), stream, Q);
+                    D4W_LAUNCH((xcorr_mm_rows<kMmKS, 0, 2, true, true>), dim3(grid_t), dim3(kMmThreads), MmGeom<kMmKS>::lds_bytes(true), stream, Q);
                 else
-                    D4W_LAUNCH((xcorr_mm_rows<kMmKS, 0, 3, true, false>), dim3(grid_t), dim3(kMmThreads), lds_of(MmGeom<kMmKS>::Arr, true), stream, Q);
+                    D4W_LAUNCH((xcorr_mm_rows<kMmKS, 0, 3, true, false>), dim3(grid_t), dim3(kMmThreads), MmGeom<kMmKS>::lds_bytes(true), stream, Q);
             }
             else if (ks <= kMmKSLong)
-                D4W_MM_LAUNCH(kMmKSLong, 0, 2, true, grid_t, lds_of(MmGeom<kMmKSLong>::Arr, true), stream, Q);
+                D4W_MM_LAUNCH(kMmKSLong, 0, 2, true, grid_t, MmGeom<kMmKSLong>::lds_bytes(true), stream, Q);
             else if (ks <= 12)
-                D4W_MM_LAUNCH(12, 0, 2, true, grid_t, lds_of(MmGeom<12>::Arr, true), stream, Q);
+                D4W_MM_LAUNCH(12, 0, 2, true, grid_t, MmGeom<12>::lds_bytes(true), stream, Q);
             else
-                D4W_MM_LAUNCH(kMmKSMax, 0, 2, true, grid_t, lds_of(MmGeom<kMmKSMax>::Arr, true), stream, Q);
+                D4W_MM_LAUNCH(kMmKSMax, 0, 2, true, grid_t, MmGeom<kMmKSMax>::lds_bytes(true), stream, Q);
         }
         return D4W_OK;
     }
@@ -704,15 +799,15 @@ int d4w_xcorr_mm_tail_f32(const float* x, int nx, int ns, const float* xnext, in
         if (rc == D4W_OK && ntpl == 2) rc = mm_one_template(P, taps + ltaps, len1, y1, rowmax1, grid, stream);
         return rc;
     }
-    const size_t lds = lds_of(MmGeom<kMmKS>::Arr, false);
     if (fused_form != 2) {
-        D4W_MM_LAUNCH_WS(false, (int)std::min<long long>(total, (long long)ncu * per_cu_ws), lds, P);
+        D4W_MM_LAUNCH_WS(false, (int)std::min<long long>(total, (long long)ncu * per_cu_ws), MmGeom<kMmKS>::lds_bytes(false), P);
         return D4W_OK;
     }
+    const size_t lds = MmGeom<kMmKS, kMmCHPair>::lds_bytes(false);
     if (ks0 <= 5)
-        D4W_MM_LAUNCH(5, kMmKS, 2, false, grid, lds, stream, P);
+        D4W_MM_LAUNCH_CH(5, kMmKS, 2, false, kMmCHPair, grid, lds, stream, P);
     else
-        D4W_MM_LAUNCH(kMmKS, kMmKS, 2, false, grid, lds, stream, P);
+        D4W_MM_LAUNCH_CH(kMmKS, kMmKS, 2, false, kMmCHPair, grid, lds, stream, P);
     return D4W_OK;
 }
 
