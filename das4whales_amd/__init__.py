@@ -12,6 +12,7 @@ from . import data_handle  # noqa: F401
 from . import stream  # noqa: F401
 from . import improcess  # noqa: F401
 from . import loc  # noqa: F401
+from . import tools  # noqa: F401
 from . import fkjit  # noqa: F401
 
 fkjit.load_cached()     # shape-specialised f-k kernels compiled on demand earlier (lib/jit/*.so)
@@ -27,4 +28,4 @@ def set_strict_reference(on=True):
     return old
 
 
-__all__ = ["dsp", "detect", "data_handle", "stream", "improcess", "loc", "set_strict_reference"]
+__all__ = ["dsp", "detect", "data_handle", "stream", "improcess", "loc", "tools", "set_strict_reference"]

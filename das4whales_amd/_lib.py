@@ -136,6 +136,11 @@ def _load():
         "d4w_row_var_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
         "d4w_snr_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
         "d4w_fx_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+        "d4w_welch_bins": (c_int, [c_int]),
+        "d4w_welch_segments": (c_int, [c_int, c_int, c_int]),
+        "d4w_welch_supported": (c_int, [c_int]),
+        "d4w_welch_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
+        "d4w_chunk_energy_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
         "d4w_stft_frames": (c_int, [c_int, c_int]),
         "d4w_stft_mag_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
         "d4w_stft_mm_eligible": (c_int, [c_int, c_int, c_int, c_int]),

@@ -1093,6 +1093,40 @@ def get_fx(trace, nfft):
     return dev.like_input(y, trace)
 
 
+def _welch(x2d, fs, nperseg, noverlap, chunk):
+    """x2d: float32 CUDA [nx, ns] -> float32 CUDA [nx, ns // chunk, nperseg // 2 + 1] (include/d4w.h d4w_welch_f32)."""
+    nx, ns = x2d.shape
+    nperseg, noverlap, chunk = int(nperseg), int(noverlap), int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk = %d must be positive" % chunk)
+    pxx = torch.empty((nx, ns // chunk, nperseg // 2 + 1), dtype=torch.float32, device=x2d.device)
+    with torch.cuda.device(x2d.device):
+        check(lib.d4w_welch_f32(dev.ptr(x2d), nx, ns, chunk, nperseg, noverlap, float(fs), dev.ptr(pxx),
+                                dev.stream_ptr(x2d)))
+    return pxx
+
+
+def welch_psd(trace, fs, nperseg=1024, noverlap=None, chunk=None):
+    """scipy.signal.welch(trace[..., j * chunk:(j + 1) * chunk], fs=fs, nperseg=nperseg, noverlap=noverlap) of every
+    row and every whole chunk of `chunk` samples (a shorter remainder is ignored), SciPy's defaults otherwise: periodic
+    Hann, each segment's mean removed, density scaling, one-sided, mean over the segments.  The general form of the
+    reference's tools.spec (tools.py:212-236).
+
+    Returns (f, Pxx): f = np.fft.rfftfreq(nperseg, 1 / fs); Pxx is [nx, nbins] for chunk=None (one chunk, the whole
+    record) and [nx, nchunks, nbins] otherwise ([nbins] / [nchunks, nbins] for a 1-D trace).  noverlap=None: nperseg // 2.
+    nperseg: even, 16..4096, prime factors <= 31 (ValueError otherwise)."""
+    x2, was1d = _rows_2d(trace)
+    nperseg = int(nperseg)
+    if noverlap is None:
+        noverlap = nperseg // 2
+    x = dev.to_device_f32(x2)
+    pxx = _welch(x, fs, nperseg, noverlap, x.shape[1] if chunk is None else chunk)
+    if chunk is None:
+        pxx = pxx[:, 0]
+    f = np.fft.rfftfreq(nperseg, 1.0 / float(fs))
+    return f, dev.like_input(pxx[0] if was1d else pxx, trace)
+
+
 def _stft_mag(x2d, n_fft, hop, bin_lo, bin_hi, want_max=True):
     """|librosa.stft| of every row: returns (S [nx, bins, frames] raw magnitudes, rowmax [nx]).  want_max=False (frame
     lengths with a two-factor register transform only): the kept bins alone are formed and rowmax is None."""

@@ -469,6 +469,33 @@ int d4w_snr_f32(const float* x, float* y, int nx, int ns, int env, float* var_ws
 int d4w_fx_f32(const float* x, float* y, int nx, int ns, int nfft, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Welch power spectral density and energy of consecutive time chunks of every row: replaces the
+ * per-chunk arithmetic of tools.spec / tools.__spec_chunk (tools.py:212-236) and
+ * tools.energy_TimeDomain / tools._energy_TimeDomain_chunk (tools.py:84-157).  One read of x, no
+ * workspace.
+ *
+ * d4w_welch_f32: for row c and chunk j < ns / chunk (a shorter remainder of the row is ignored)
+ *     pxx[c][j][:] = scipy.signal.welch(x[c, j*chunk:(j+1)*chunk], fs=fs, nperseg=nperseg,
+ *                                       noverlap=noverlap)[1]
+ *   with SciPy's defaults: periodic Hann window, detrend='constant' (each segment's own mean, formed
+ *   in float64, leaves the samples before the window), nfft = nperseg, segments every
+ *   nperseg - noverlap samples while a whole one fits (d4w_welch_segments(chunk, nperseg, noverlap)
+ *   of them), average='mean', scaling='density' = 1 / (fs sum(w^2)), one-sided with every bin but DC
+ *   and Nyquist doubled.  pxx is DEVICE [nx][ns / chunk][d4w_welch_bins(nperseg) = nperseg/2 + 1].
+ *   Accepted: nperseg even, 16 <= nperseg <= 4096, every prime factor of nperseg <= 31
+ *   (d4w_welch_supported(nperseg) == 1), 0 <= noverlap < nperseg, nperseg <= chunk <= ns, fs > 0;
+ *   D4W_EINVAL otherwise.
+ * d4w_chunk_energy_f32: e[c][j] = sum(x[c, j*chunk : min((j+1)*chunk, ns)]**2), summed in float64;
+ *   the last chunk may be short.  e is DEVICE [nx][ceil(ns / chunk)];  1 <= chunk <= ns.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_welch_bins(int nperseg);
+int d4w_welch_segments(int n, int nperseg, int noverlap);
+int d4w_welch_supported(int nperseg);
+int d4w_welch_f32(const float* x, int nx, int ns, int chunk, int nperseg, int noverlap, double fs,
+                  float* pxx, void* stream);
+int d4w_chunk_energy_f32(const float* x, int nx, int ns, int chunk, float* e, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Spectrograms and spectrogram correlation: replaces dsp.get_spectrogram (dsp.py:41-78),
  * detect.get_sliced_nspectrogram (detect.py:334-408), detect.xcorr2d (detect.py:579-602),
  * detect.xcorr (detect.py:605-647) and the per-channel loop of
