@@ -744,9 +744,12 @@ __global__ __launch_bounds__(kSpThreads) void row_median(const float* __restrict
 // ---------------------------------------------------------------------------------------------
 // spectrogram x kernel correlation along time, summed over frequency:
 //   raw[c][t] = sum_f sum_j S[c][f][t + j - off] K[f][j]   (S = 0 outside [0, nt)),  t < nout
-//   out = max(raw, 0) / (med[c] * nk)                      (detect.py:597-600)
-// off = nk/2 reproduces fftconvolve(S, flip(K, 1), 'same', axes=1); off = 0 with nout = nt-nk+1
-// and zero_ends reproduces detect.xcorr (detect.py:632-644: first and last value forced to 0).
+//   zero_ends == 0:  out = max(raw, 0) / (med[c] * nk)     (detect.py:597-600: clipped, then divided)
+//   zero_ends != 0:  out = max(raw / (med[c] * nk), 0), first and last value forced to 0
+//                                                          (detect.py:632-645: divided, then clipped)
+// The two differ when med[c] < 0 (a spectrogram in dB): the first form is then <= 0, the second >= 0.
+// off = nk/2, nout = nt, zero_ends = 0 reproduces detect.xcorr2d (fftconvolve(S, flip(K, 1), 'same', axes=1));
+// off = 0, nout = nt-nk+1, zero_ends = 1 reproduces detect.xcorr.
 // ---------------------------------------------------------------------------------------------
 constexpr int kScThreads = 128, kScPer = 4, kScTile = kScThreads * kScPer;      // 512 correlation lags per workgroup
 constexpr int kScLdsFloats = 2560;          // a few strip rows at a time: a small footprint keeps ~30 waves on a CU
@@ -826,10 +829,16 @@ __global__ __launch_bounds__(kScThreads) void spectro_corr(const float* __restri
     for (int qq = 0; qq < kScPer; ++qq) {
         const int t = t0 + kScPer * tid + qq;
         if (t < nout) {
-            float v = acc[qq] / (med[blockIdx.y] * (float)nk);
-            if (zero_ends && (t == 0 || t == nout - 1)) v = 0.f;
-            if (v < 0.f) v = 0.f;                                    // NaN (0/0 on an all-zero row) passes through
-            out[(size_t)blockIdx.y * nout + t] = v;
+            // the two reference forms clip at different places, which shows once the median is negative (a dB spectrogram):
+            // xcorr2d clips the raw sum and then divides, xcorr divides, zeroes its ends and then clips
+            float v = acc[qq];
+            if (!zero_ends && v < 0.f) v = 0.f;
+            v /= med[blockIdx.y] * (float)nk;
+            if (zero_ends) {
+                if (t == 0 || t == nout - 1) v = 0.f;
+                if (v < 0.f) v = 0.f;
+            }
+            out[(size_t)blockIdx.y * nout + t] = v;                  // NaN (0/0 on an all-zero row) passes through both forms
         }
     }
 }

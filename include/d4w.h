@@ -512,8 +512,10 @@ int d4w_chunk_energy_f32(const float* x, int nx, int ns, int chunk, float* e, vo
  * d4w_row_median_f32: med[c] = np.median(v[c][0:per_row]).
  * d4w_spectrocorr_f32:
  *   raw[c][t] = sum_f sum_j S[c][f][t + j - off] K[f][j]  (zero outside the spectrogram), t < nout
- *   out[c][t] = max(raw, 0) / (med[c] * nk);  zero_ends != 0 also forces out[c][0] = out[c][nout-1] = 0.
- *   off = nk/2, nout = nt: detect.xcorr2d;  off = 0, nout = nt-nk+1, zero_ends: detect.xcorr.
+ *   zero_ends == 0: out[c][t] = max(raw, 0) / (med[c] * nk)  (clipped, then divided: detect.py:599-600);
+ *   zero_ends != 0: out[c][t] = max(raw / (med[c] * nk), 0) with out[c][0] = out[c][nout-1] = 0  (divided, then
+ *   clipped: detect.py:642-645).  The forms differ only for med[c] < 0.  An all-zero row gives NaN (0 / 0) in both.
+ *   off = nk/2, nout = nt, zero_ends = 0: detect.xcorr2d;  off = 0, nout = nt-nk+1, zero_ends = 1: detect.xcorr.
  *   S [nx][nf][nt], K [nf][nk], med [nx], out [nx][nout], all DEVICE float32.
  * ------------------------------------------------------------------------------------------ */
 int d4w_stft_frames(int ns, int hop);
