@@ -15,7 +15,7 @@
 // Toeplitz matrix, zero outside the band, resident in registers for the whole launch) and B[u][a] = x[16 a + u]
 // (overlapping windows of the row, read straight out of an LDS copy of the row chunk: lane (a, g) takes the 8
 // consecutive samples 16 a + 32 kk + 8 g .. + 7 as ONE 16-byte LDS read).  v_mfma_f32_16x16x32_f16 does 16 384
-// flop per instruction; 11 k-steps x 3 products per 256 lags leave the matrix pipe ~35 % busy at the HBM rate,
+// flop per instruction; 11 k-steps x 3 products per 256 lags leave the matrix pipe 43.8 % busy at the HBM rate,
 // the vector ALUs only convert and store, and the kernel is a plain stream: 4 B read + 8 B written per sample.
 //
 // float32 through binary16 factors.  Every operand is split into two binary16 values, v = hi + lo 2^-11
@@ -26,24 +26,21 @@
 // nothing overflows binary16; small values use its subnormals, which the conversions and the matrix instruction keep.  Measured against a float64 correlation the result is as close as the float32
 // FFT kernel's (tests/test_rowops_gpu.py).
 //
-// Launch shape.  Persistent workgroups (256 threads, 4 waves) walk chunks of 4096 lags of one row (8192 where two templates
-// share the launch: two groups of 4096, each staged with its own halo, scale and prefix carry -- MmGeom); the chunk's
-// 4096 + 192 samples are loaded one chunk AHEAD into registers (17 floats per lane), converted and written to
-// one of two LDS buffers (hi / lo arrays in sample order: the four lane groups of a fragment read hit 16 different
-// 16-byte slots each), ONE barrier per chunk, then every wave runs four 16 x 16 tiles (256 lags each,
-// both templates) and streams the results out with 16-byte non-temporal stores (lane (a, g) holds lags
-// 16 a + 4 g .. + 3: 1 KiB contiguous per wave and template).  Chunks are dealt to the XCDs in contiguous
-// ranges, so the 192-sample halo of a chunk is an L2 hit.
+// Launch shape.  Persistent workgroups (256 threads, 4 waves) walk a row in CHUNKS of CH lags: 4096 (kMmCH) for one template,
+// 8192 (kMmCHPair) where two templates share the launch.  A chunk is G = CH / 4096 GROUPS of 4096 lags (kMmGroup), each
+// staged with its own halo of 32 KS samples, its own scale and its own prefix carry (MmGeom), so a lag's arithmetic does not
+// depend on CH.  The chunk's CH + halo samples are loaded one chunk AHEAD into registers, converted and written to one of
+// two LDS buffers (hi / lo arrays in sample order: the four lane groups of a fragment read hit 16 different 16-byte slots
+// each), ONE barrier per chunk, then every wave runs every fourth 16 x 16 tile (256 lags each, both templates) and streams
+// the results out with 16-byte non-temporal stores (lane (a, g) holds lags 16 a + 4 g .. + 3: 1 KiB contiguous per wave and
+// template).  Chunks are dealt to the XCDs in contiguous ranges, so the halo of a chunk is an L2 hit.
 #include <cstdlib>
 
 #include "mm_common.h"
 
 namespace d4w {
 
-#ifndef D4W_MM_CH
-#define D4W_MM_CH 4096
-#endif
-constexpr int kMmCH = D4W_MM_CH;                 // lags per chunk of the one-template kernels
+constexpr int kMmCH = 4096;                      // lags per chunk of the one-template kernels
 constexpr int kMmCHPair = 8192;                  // ... of the two-template kernels (0.22 ms faster there, 2.4 ms slower for one template: DESIGN 3.3)
 constexpr int kMmGroup = 4096;                   // a longer chunk is staged, scaled and prefix-summed in GROUPS of this many lags: the arithmetic of a lag
                                                  // does not depend on the chunk length its kernel walks the row in
@@ -76,11 +73,10 @@ struct MmGeom {
     }
     static_assert(CH % (4 * kMmThreads) == 0 && GL % (4 * kMmThreads) == 0 && Halo <= 4 * kMmThreads, "a group is whole loads; its halo lies in one");
 };
-// LDS index of sample h of the chunk: the plain order.  ds_read_b128 is served in four NON-contiguous 16-lane groups
+// Sample h of a group's stage sits at index h of the LDS array: the plain order.  ds_read_b128 is served in four NON-contiguous 16-lane groups
 // ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ...: MI355X_MICROARCH.md, LDS), and with lane (a, g) reading the 16-byte
 // slot 2 a + g (+ const) every group touches 16 different slots: no bank conflict.  (Round 4's first build padded 16 B
 // per 256 B for contiguous groups: 61 % of its LDS cycles were conflicts, profiles/r04a/pmc_sq_matched_filter.txt.)
-__host__ __device__ constexpr int mm_pidx(int h) { return h; }
 
 struct MmArgs {
     const float* x;         // [nx][ns]
@@ -99,6 +95,10 @@ struct MmArgs {
     // TAIL kernels (the zero-padded template's constant tail, detect.py:158, added in the epilogue -- see xcorr_mm_rows):
     float tail0, tail1;             // mean(t) / max|t| of template 0 / 1 over its zero-padded length (0: nothing to add)
 };
+
+// a wave runs every fourth tile of 256 lags: the ti-th tile of wave wv.  (A function, not the expression in place: written out
+// in the tile's epilogue, hipcc schedules the TAIL kernels differently.)
+__device__ __forceinline__ int mm_tile(int wv, int ti) { return wv + 4 * ti; }
 
 // inclusive prefix sum over the 64 lanes of a wave: four row_shr steps inside the 16-lane DPP rows, then row_bcast:15 /
 // row_bcast:31 carry the row totals on (six v_add_f32 with DPP operands, no LDS traffic)
@@ -148,17 +148,14 @@ __device__ __forceinline__ float mm_wave_scan(float v) {
 //     rows each) and 512 streams a row apart instead of 8 compact windows.
 // WMAX: the epilogue also leaves the rows' maxima (P.rowmax0 / rowmax1) -- a separate instantiation, so that the kernels without
 // them carry neither the branches nor the registers (round 5 had it as a kernel-argument branch in every tile's epilogue).
-// WSPLIT (round 6; measured slower, kept behind D4W_MM_FUSED=3): two templates with the WAVES split between them -- waves 0, 1 run template 0 and waves 2, 3 template 1, eight
-// tiles each, instead of every wave running both templates on four tiles.  A wave then keeps ONE template's Toeplitz fragments
-// (44 registers instead of 88): the kernel fits three workgroups per compute unit like the one-template kernel (163 against 201
-// registers), and the third workgroup is worth 8.5 % to that kernel (profiles/r06l/mm_wgs.txt).  The matrix work per wave is the
-// same (144 instructions per chunk); the sample fragments are read from LDS by two waves instead of one -- and that is what it
-// loses on: 6.32 against 6.11 ms for the kernel where every wave runs both templates (profiles/r06m/mm_wave_split.txt).
-// Instantiated as <KS, 0, 3, ., ., true>: the one-template code with the template, output, tail coefficient and row maxima
-// chosen by the wave.
-template <int KS0, int KS1, int WPS, bool TAIL = false, bool WMAX = false, bool WSPLIT = false, int CH = kMmCH>
+// (A form with the WAVES split between two templates at three workgroups per CU was built in round 6 and measured slower,
+// 6.32 against 6.11 ms: DESIGN.md 3.3, profiles/r06m.)
+//
+// Probe builds (scripts/probe/mm_variants.sh), timing only -- each returns WRONG values: D4W_MM_V_NOCONV awaits the loads and
+// converts nothing, D4W_MM_V_NOMFMA leaves out the matrix products, D4W_MM_V_NOSTORE writes nothing.  They stay until the
+// phase table they exist for (profiles/mm_pair/README.md, step 4) has been measured on hardware.
+template <int KS0, int KS1, int WPS, bool TAIL = false, bool WMAX = false, int CH = kMmCH>
 __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
-    static_assert(!(WSPLIT && KS1 > 0), "the wave-split kernel is the one-template code run by two wave pairs");
     constexpr int KSM = KS0 > KS1 ? KS0 : KS1;
     using GEO = MmGeom<KSM, CH>;
     constexpr int kMmHalo = GEO::Halo, kMmStage = GEO::Stage, kMmQ = GEO::Q, kMmLastQ = GEO::LastQ, kMmArr = GEO::Arr;
@@ -174,18 +171,13 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
     const int lane = tid & 63, wv = mm_uniform(tid >> 6);
     const int n16 = lane & 15, g = lane >> 4;
     const int ns = P.ns;
-    const int tsel = WSPLIT ? (wv >> 1) : 0;                        // WSPLIT: the template this wave runs (wave-uniform)
 
     // ---- the templates' Toeplitz fragments: A_t[kk][i = n16][u = 32 kk + 8 g + j] = t[u - i] / ts_t, split hi / lo
     mm_h8 a0h[KS0], a0l[KS0];
     mm_h8 a1h[KS1 ? KS1 : 1], a1l[KS1 ? KS1 : 1];
     float osc0 = 1.f, osc1 = 1.f;                                   // output scales: the power of two taken out of the taps
     // TAIL: whole rows (row = workgroup + k x grid), their chunks in order; else chunk lo_c + wq + k nq of the XCD's range
-#ifdef D4W_MM_V_TAIL_DEALT          // (probe builds: the tail kernels with the chunks dealt over the grid -- WRONG prefixes, timing only)
-    constexpr bool kRows = false;
-#else
     constexpr bool kRows = TAIL;
-#endif
     // ---- the chunks of this workgroup, walked as (row, chunk inside the row): wave-uniform integers moved on by additions and
     // one compare per chunk -- every division is here, ahead of the loop
     const int nchunk = (ns + CH - 1) / CH;
@@ -229,9 +221,9 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
         for (int i = tid; i < 2 * TLP; i += kMmThreads) {
             const int t = i / TLP, u = i - t * TLP - 15;
             const int L = t ? P.len1 : P.len0;
-            float tv = (u >= 0 && u < L && (t == 0 || KS1 > 0 || WSPLIT)) ? P.taps[(size_t)t * P.ltaps + u] : 0.f;
+            float tv = (u >= 0 && u < L && (t == 0 || KS1 > 0)) ? P.taps[(size_t)t * P.ltaps + u] : 0.f;
             if constexpr (TAIL) {                                   // the term inside a block of 16 lags: t[d] + tail for every d < L
-                if (u < L && (t == 0 || KS1 > 0 || WSPLIT)) tv += t ? P.tail1 : P.tail0;
+                if (u < L && (t == 0 || KS1 > 0)) tv += t ? P.tail1 : P.tail0;
             }
             tl[i] = tv;
         }
@@ -257,7 +249,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
                 });
             });
         };
-        build(tl + (WSPLIT ? tsel * TLP : 0), WSPLIT && tsel ? P.len1 : P.len0, a0h, a0l, std::integral_constant<int, KS0>{}, osc0);
+        build(tl, P.len0, a0h, a0l, std::integral_constant<int, KS0>{}, osc0);
         if constexpr (KS1 > 0) build(tl + TLP, P.len1, a1h, a1l, std::integral_constant<int, KS1>{}, osc1);
         __syncthreads();                                            // the row buffers take this space over
     }
@@ -336,7 +328,6 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
 
     if (more_n) issue();
     int buf = 0;
-    constexpr bool want_max = WMAX;
     // TAIL: prefix of the normalised row at the chunk's first sample, a float64 kept as two wave-uniform floats (scalar registers)
     float pst_hi = 0.f, pst_lo = 0.f;
     for (bool more = more_n; more; more = more_n) {
@@ -402,11 +393,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             const float mlg = -mu.lo * gsc[gi];
             // ((x - hi) - lo) g as (x - hi) g - lo g: the two-float mean at the instruction count of a float32 one (x - hi is
             // exact where the offset dominates, the product is rounded once)
-#ifdef D4W_MM_V_FLOATMEAN          // (probe builds: what the two-float mean costs)
-            s[0] = (v.x - mu.hi) * gsc[gi]; s[1] = (v.y - mu.hi) * gsc[gi]; s[2] = (v.z - mu.hi) * gsc[gi]; s[3] = (v.w - mu.hi) * gsc[gi];
-#else
             s[0] = fmaf(v.x - mu.hi, gsc[gi], mlg); s[1] = fmaf(v.y - mu.hi, gsc[gi], mlg); s[2] = fmaf(v.z - mu.hi, gsc[gi], mlg); s[3] = fmaf(v.w - mu.hi, gsc[gi], mlg);
-#endif
             // the next file's head (or statistics that are not the rows' own, D4W_MM_CLAMP=1) may leave |v| beyond binary16's
             // range: inf - inf would turn a whole tile into NaN where the float32 forms stay finite; one v_med3_f32 per
             // sample, only where asked for (a kernel argument: a scalar branch)
@@ -420,34 +407,23 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             float s[4] = {0.f, 0.f, 0.f, 0.f};
             const bool mine = q < kMmQ - 1 || tid < kMmLastQ;
             const int at = 4 * (tid + q * kMmThreads);              // the lane's first sample inside the chunk
-#ifdef D4W_MM_V_NOCONV              // (probe builds: loads awaited, nothing converted or written to LDS -- WRONG values, timing only)
+#ifdef D4W_MM_V_NOCONV              // (probe build, see above the kernel)
             if (mine && pre[q].x == 1.2345e30f) {
 #else
             if (mine) {
 #endif
                 scaled(pre[q], at, std::integral_constant<int, gq>{}, s);
                 // group gq's stage starts at gq (GL + halo) in the arrays: sample `at` of the chunk sits gq halos further on
-#ifdef D4W_MM_V_OLDSPLIT
-                mm_half h[4], l[4];
-                static_for<4>([&](auto ee) { constexpr int e = decltype(ee)::value; mm_split(s[e], h[e], l[e]); });
-                mm_put4(bh + mm_pidx(at + gq * kMmHalo), h);
-                mm_put4(bl + mm_pidx(at + gq * kMmHalo), l);
-#else
-                mm_split_put4(s, bh + mm_pidx(at + gq * kMmHalo), bl + mm_pidx(at + gq * kMmHalo));
-#endif
+                mm_split_put4(s, bh + (at + gq * kMmHalo), bl + (at + gq * kMmHalo));
                 if constexpr (q >= QG && q < G * QG && q % QG == 0) {              // ... and once more as the halo of the group before, in that group's scale
                     if (tid < kMmHalo / 4) {
                         float h4[4];
                         scaled(pre[q], at, std::integral_constant<int, gq - 1>{}, h4);
-                        mm_split_put4(h4, bh + mm_pidx(at + (gq - 1) * kMmHalo), bl + mm_pidx(at + (gq - 1) * kMmHalo));
+                        mm_split_put4(h4, bh + (at + (gq - 1) * kMmHalo), bl + (at + (gq - 1) * kMmHalo));
                     }
                 }
             }
-#ifdef D4W_MM_V_TAIL_NOSCAN         // (probe builds: no prefix scan, no tail term -- timing only)
-            if constexpr (false) {
-#else
             if constexpr (TAIL && q < G * QG) {                     // the chunk's own samples (the halo adds no block of lags)
-#endif
                 // prefix of the scaled samples at every fourth lane = every block of 16 samples, inside this wave's segment
                 const float t4 = (s[0] + s[1]) + (s[2] + s[3]);
                 const float inc = mm_wave_scan(t4);
@@ -460,7 +436,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
         if (more_n) issue();
         lds_barrier();
         // ---- CH / 256 tiles of 256 lags, a quarter per wave: C[i][a] (+)= A[i][u] B[u][a]
-        float* ya = ((WSPLIT && tsel) ? P.y1 : P.y0) + roff;
+        float* ya = P.y0 + roff;
         float* yb = KS1 ? P.y1 + roff : nullptr;
         const bool valign = ((reinterpret_cast<uintptr_t>(ya + c0) & 15) == 0) && (!KS1 || (reinterpret_cast<uintptr_t>(yb + c0) & 15) == 0);
         float oxs[G], o0[G], o1[G];
@@ -477,14 +453,12 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
         // the wave's tiles as ONE software pipeline over (tile, k-step): the fragment pair of step s + PF is requested
         // before the six products of step s are issued (mm_sched_fence keeps hipcc from sinking the reads back to their use),
         // so an LDS round trip hides under 12 matrix instructions instead of stalling the wave at every k-step
-        constexpr int TPW = WSPLIT ? 2 : 4;                         // a wave runs every TPW-th tile
-        constexpr int NTW = CH / 256 / TPW, NST = NTW * KSM, PF = 2;
-        constexpr int TG = GL / 256;                                // tiles per group (a multiple of TPW: the wave's ti-th tile lies in group TPW ti / TG)
-        auto tile_of = [&](int ti) { return WSPLIT ? (wv & 1) + 2 * ti : wv + 4 * ti; };     // the wave's ti-th tile
+        constexpr int NTW = CH / 256 / 4, NST = NTW * KSM, PF = 2;
+        constexpr int TG = GL / 256;                                // tiles per group (a multiple of 4: the wave's ti-th tile lies in group 4 ti / TG)
         auto frag = [&](const mm_half* arr, int ti, int kk) -> mm_h8 {
-            const int T = tile_of(ti);
+            const int T = mm_tile(wv, ti);
             const int gr = 32 * T + 2 * n16 + g + 4 * kk;           // 16-byte granule: sample 256 T + 16 n16 + 32 kk + 8 g of the chunk
-            return *reinterpret_cast<const mm_h8*>(arr + mm_pidx(8 * gr + (TPW * ti / TG) * kMmHalo));
+            return *reinterpret_cast<const mm_h8*>(arr + (8 * gr + (4 * ti / TG) * kMmHalo));
         };
         mm_h8 fh[PF + 1], fl[PF + 1];
         static_for<PF>([&](auto ss) {
@@ -503,7 +477,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             }
             mm_sched_fence();
             const mm_h8 xh = fh[s_ % (PF + 1)], xl = fl[s_ % (PF + 1)];
-#ifndef D4W_MM_V_NOMFMA             // (probe builds without the matrix products: WRONG values, timing only)
+#ifndef D4W_MM_V_NOMFMA             // (probe build)
             if constexpr (kk < KS0) {
                 c0h = mm_mfma(a0h[kk], xh, c0h);
                 c0l = mm_mfma(a0h[kk], xl, c0l);
@@ -519,8 +493,8 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
 #endif
             mm_sched_fence();
             if constexpr (kk == KSM - 1) {                          // the tile is complete: scale, combine, stream out
-                constexpr int tg = TPW * ti / TG;                   // the tile's group
-                const int T = tile_of(ti);
+                constexpr int tg = 4 * ti / TG;                     // the tile's group
+                const int T = mm_tile(wv, ti);
                 const int kl = 256 * T + 16 * n16 + 4 * g;          // this lane's four lags inside the chunk ...
                 const int k = c0 + kl;                              // ... and inside the row
                 if constexpr (ti == 0) {
@@ -552,11 +526,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
                 }
                 float r0[4], r1[4];
                 float a0 = 0.f, a1 = 0.f;                           // TAIL: tail_t x (prefix at the block's first sample), the same for the lane's four lags
-#ifdef D4W_MM_V_TAIL_NOSCAN
-                if constexpr (false) {
-#else
                 if constexpr (TAIL) {
-#endif
                     // tile T = the segment this wave converted: row prefix at the group + segment offset + block prefix
 #ifdef D4W_EMU
                     const float so = __shfl(segoff[tg], T - tg * TG);
@@ -566,7 +536,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
                     // (tile T = segment T of the stage = load T / 4 of wave T % 4)
                     const int pi = G == 1 ? kMmThreads * (T >> 2) + 64 * (T & 3) + 4 * n16 : (kMmThreads / 4) * (T >> 2) + 16 * (T & 3) + n16;
                     const float pbk = fmaf(so + pb[buf * kPb + pi], oxs[tg], pstg[tg]);
-                    a0 = ((WSPLIT && tsel) ? P.tail1 : P.tail0) * pbk;
+                    a0 = P.tail0 * pbk;
                     a1 = P.tail1 * pbk;
                 }
                 static_for<4>([&](auto rr) {
@@ -576,7 +546,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
                     if constexpr (KS1 > 0) r1[r] = fmaf(fmaf(mm_get(c1l, r), kMmLoInv, mm_get(c1h, r)), o1[tg], a1);
                 });
                 c0h = mm_zero(); c0l = mm_zero(); c1h = mm_zero(); c1l = mm_zero();
-#ifdef D4W_MM_V_NOSTORE             // (probe builds that write nothing: timing only)
+#ifdef D4W_MM_V_NOSTORE             // (probe build)
                 if (r0[0] != 1.2345e30f) { }
                 else
 #endif
@@ -587,16 +557,12 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
                     }
                     mm_store4(ya + k, r0[0], r0[1], r0[2], r0[3]);
                     if constexpr (KS1 > 0) mm_store4(yb + k, r1[0], r1[1], r1[2], r1[3]);
-                    if (want_max) {
+                    if (WMAX) {
                         vmax0 = fmaxf(vmax0, fmaxf(fmaxf(r0[0], r0[1]), fmaxf(r0[2], r0[3])));
-#ifndef D4W_MM_V_NONAN
                         vsum += (r0[0] + r0[1]) + (r0[2] + r0[3]);
-#endif
                         if constexpr (KS1 > 0) {
                             vmax1 = fmaxf(vmax1, fmaxf(fmaxf(r1[0], r1[1]), fmaxf(r1[2], r1[3])));
-#ifndef D4W_MM_V_NONAN
                             vsum += (r1[0] + r1[1]) + (r1[2] + r1[3]);
-#endif
                         }
                     }
                 } else {                                            // a row end or an unaligned row (tiles beyond the row: nothing)
@@ -605,7 +571,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
                             const float v0 = (KS1 == 0 && P.accumulate) ? ya[k + r] + r0[r] : r0[r];
                             ya[k + r] = v0;
                             if constexpr (KS1 > 0) yb[k + r] = r1[r];
-                            if (want_max) {
+                            if (WMAX) {
                                 vmax0 = fmaxf(vmax0, v0);
                                 vsum += v0;
                                 if constexpr (KS1 > 0) { vmax1 = fmaxf(vmax1, r1[r]); vsum += r1[r]; }
@@ -614,7 +580,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
                 }
             }
         });
-        if (want_max) {                                             // one atomic per wave, chunk and template
+        if (WMAX) {                                             // one atomic per wave, chunk and template
             for (int o = 32; o > 0; o >>= 1) {
                 vmax0 = fmaxf(vmax0, __shfl_xor(vmax0, o));
                 if constexpr (KS1 > 0) vmax1 = fmaxf(vmax1, __shfl_xor(vmax1, o));
@@ -624,7 +590,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             // samples, so a NaN in one is a NaN in the other.
             const bool bad = __any(vsum != vsum);
             if (lane == 0) {
-                mm_atomic_fmax(((WSPLIT && tsel) ? P.rowmax1 : P.rowmax0) + row, bad ? __uint_as_float(0x7FC00000u) : vmax0);
+                mm_atomic_fmax(P.rowmax0 + row, bad ? __uint_as_float(0x7FC00000u) : vmax0);
                 if constexpr (KS1 > 0) mm_atomic_fmax(P.rowmax1 + row, bad ? __uint_as_float(0x7FC00000u) : vmax1);
             }
         }
@@ -636,51 +602,78 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
 
 using namespace d4w;
 
-extern "C" {
+// ---- the launch table.  Every rule is written once:
+//   mm_wps           workgroups per CU an instantiation's registers are budgeted for
+//   mm_launch        one launch: row maxima or not, the LDS size of the instantiation's own geometry
+//   mm_one_section   one template of <= 497 taps -> the 6-, 8-, 12- or 16-step kernel
+//   mm_pair          two templates of <= 177 taps -> the <5, 6> or <6, 6> kernel on chunks of kMmCHPair lags
+//   mm_one_template  one template of any support: sections of equal length through mm_one_section
+// and d4w_xcorr_mm_tail_f32 below chooses the grid and between mm_pair and mm_one_template.
 
-int d4w_xcorr_mm_max_support(void) { return kMmSection * kMmMaxSections; }
+// Two templates keep the Toeplitz fragments of both in registers: two workgroups per CU (a 168-register build for three spills
+// and ran 8.5 ms against 6.6).  One template of <= 6 k-steps fits three -- with the tail, only without the row maxima.  The
+// deeper one-template kernels: two.
+constexpr int mm_wps(int ks0, int ks1, bool tail, bool wmax) { return (ks1 == 0 && ks0 <= kMmKS && !(tail && wmax)) ? 3 : 2; }
+
+template <int KS0, int KS1, bool TAIL, bool WMAX, int CH>
+static int mm_launch_as(const MmArgs& Q, int grid, void* stream) {
+    constexpr size_t lds = MmGeom<(KS0 > KS1 ? KS0 : KS1), CH>::lds_bytes(TAIL);
+    void (*kern)(MmArgs) = xcorr_mm_rows<KS0, KS1, mm_wps(KS0, KS1, TAIL, WMAX), TAIL, WMAX, CH>;
+    // (more than 64 KiB of LDS per workgroup has to be asked for)
+    if (lds > 64 * 1024) D4W_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    D4W_LAUNCH(kern, dim3(grid), dim3(kMmThreads), lds, stream, Q);
+    return D4W_OK;
+}
+
+template <int KS0, int KS1, bool TAIL, int CH = kMmCH>
+static int mm_launch(const MmArgs& Q, int grid, void* stream) {
+    return Q.rowmax0 ? mm_launch_as<KS0, KS1, TAIL, true, CH>(Q, grid, stream) : mm_launch_as<KS0, KS1, TAIL, false, CH>(Q, grid, stream);
+}
+
+template <bool TAIL>
+static int mm_one_section(const MmArgs& Q, int grid, void* stream) {
+    const int ks = ceil_div(Q.len0 + 15, 32);
+    if (ks <= kMmKS) return mm_launch<kMmKS, 0, TAIL>(Q, grid, stream);
+    if (ks <= kMmKSLong) return mm_launch<kMmKSLong, 0, TAIL>(Q, grid, stream);
+    if (ks <= 12) return mm_launch<12, 0, TAIL>(Q, grid, stream);
+    return mm_launch<kMmKSMax, 0, TAIL>(Q, grid, stream);
+}
+
+template <bool TAIL>
+static int mm_pair(const MmArgs& P, int grid, void* stream) {
+    if (ceil_div(P.len0 + 15, 32) <= 5) return mm_launch<5, kMmKS, TAIL, kMmCHPair>(P, grid, stream);
+    return mm_launch<kMmKS, kMmKS, TAIL, kMmCHPair>(P, grid, stream);
+}
 
 // one template of any support <= d4w_xcorr_mm_max_support(): sections of kMmSection taps, the first one overwriting y, the
-// later ones (x shifted by the section's first tap) accumulating into it
-// launch of xcorr_mm_rows<KS0, KS1, WPS, TAIL> with or without the row maxima
-#define D4W_MM_LAUNCH(KS0, KS1, WPS, TAIL, grid, lds, stream, Q) D4W_MM_LAUNCH_CH(KS0, KS1, WPS, TAIL, kMmCH, grid, lds, stream, Q)
-// ... walking the rows in chunks of CH lags (more than 64 KiB of LDS per workgroup has to be asked for)
-#define D4W_MM_LAUNCH_CH(KS0, KS1, WPS, TAIL, CH, grid, lds, stream, Q)                                                       \
-    do {                                                                                                                      \
-        void (*kern_)(MmArgs) = (Q).rowmax0 ? xcorr_mm_rows<KS0, KS1, WPS, TAIL, true, false, CH>                              \
-                                            : xcorr_mm_rows<KS0, KS1, WPS, TAIL, false, false, CH>;                            \
-        if ((lds) > 64 * 1024) D4W_HIP(hipFuncSetAttribute((const void*)kern_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds))); \
-        D4W_LAUNCH(kern_, dim3(grid), dim3(kMmThreads), lds, stream, Q);                                                       \
-    } while (0)
-
-static int mm_one_template(MmArgs P, const float* taps, int len, float* y, float* rowmax, int grid, void* stream) {
+// later ones (x shifted by the section's first tap) accumulating into it.  tails: the TAIL kernels, with this template's
+// coefficient (the caller has checked the support: one section)
+static int mm_one_template(MmArgs Q, const float* taps, int len, bool tails, float tail, float* y, float* rowmax, int grid, void* stream) {
     const int nsec = (len <= 32 * kMmKSMax - 15) ? 1 : ceil_div(len, kMmSection);
     // sections of equal length (a multiple of 16 taps, so that the shifted 16-byte loads stay aligned): 700 taps run as
     // 352 + 348 through the 12-step kernel twice instead of 496 + 204 through the 16- and the 8-step kernels
     const int per = (nsec == 1) ? len : 16 * ceil_div(ceil_div(len, nsec), 16);
+    Q.y0 = y;
+    Q.y1 = nullptr;
+    Q.rowmax1 = nullptr;
+    Q.tail0 = tail;
+    Q.tail1 = 0.f;
     for (int j = 0; j < nsec; ++j) {
         const int first = j * per;
-        MmArgs Q = P;
         Q.taps = taps + first;
         Q.len0 = Q.len1 = std::min(per, len - first);
-        Q.y0 = y;
-        Q.y1 = nullptr;
         Q.shift = first;
         Q.accumulate = j > 0;
         Q.rowmax0 = (j == nsec - 1) ? rowmax : nullptr;             // the maxima of the finished sums
-        Q.rowmax1 = nullptr;
-        const int ks = ceil_div(Q.len0 + 15, 32);
-        if (ks <= kMmKS)
-            D4W_MM_LAUNCH(kMmKS, 0, 3, false, grid, MmGeom<kMmKS>::lds_bytes(false), stream, Q);
-        else if (ks <= kMmKSLong)
-            D4W_MM_LAUNCH(kMmKSLong, 0, 2, false, grid, MmGeom<kMmKSLong>::lds_bytes(false), stream, Q);
-        else if (ks <= 12)
-            D4W_MM_LAUNCH(12, 0, 2, false, grid, MmGeom<12>::lds_bytes(false), stream, Q);
-        else
-            D4W_MM_LAUNCH(kMmKSMax, 0, 2, false, grid, MmGeom<kMmKSMax>::lds_bytes(false), stream, Q);
+        const int rc = tails ? mm_one_section<true>(Q, grid, stream) : mm_one_section<false>(Q, grid, stream);
+        if (rc != D4W_OK) return rc;
     }
     return D4W_OK;
 }
+
+extern "C" {
+
+int d4w_xcorr_mm_max_support(void) { return kMmSection * kMmMaxSections; }
 
 int d4w_xcorr_mm_f32(const float* x, int nx, int ns, const float* xnext, int ld_next, int n_next, const double* mean,
                      const float* maxabs, const float* taps, int ntpl, int ltaps, int len0, int len1, float* y0, float* y1,
@@ -728,87 +721,26 @@ int d4w_xcorr_mm_tail_f32(const float* x, int nx, int ns, const float* xnext, in
         D4W_HIP(hipMemsetD32Async((hipDeviceptr_t)rowmax0, (int)0xFF800000u, (size_t)nx, (hipStream_t)stream));
         if (ntpl == 2) D4W_HIP(hipMemsetD32Async((hipDeviceptr_t)rowmax1, (int)0xFF800000u, (size_t)nx, (hipStream_t)stream));
     }
-    // persistent workgroups per compute unit: 2 for two templates (the Toeplitz fragments of both templates stay in
-    // registers; a 168-register build for three workgroups spills and ran 8.5 ms against 6.6), 3 for one template
-    // (149 VGPRs), 2 for the deeper one-template kernels.  D4W_MM_WGS overrides the count (measurements).
+    // persistent workgroups per compute unit: 2 for two templates, 3 for one template of <= 6 k-steps, 2 for the deeper
+    // one-template kernels (a second template of a pair that runs alone included).  The 6-step kernel with the tail AND the row
+    // maxima is budgeted for 2 (mm_wps) and still launched on this grid of 3 per CU: kept as it was measured, a decision
+    // for another day.  D4W_MM_WGS overrides the count (measurements).
     static const int env_wgs = [] { const char* v = getenv("D4W_MM_WGS"); const int n = v ? atoi(v) : 0; return n < 0 ? 0 : (n > 8 ? 8 : n); }();
     const int ks0 = ceil_div(len0 + 15, 32), ks1 = ceil_div(len1 + 15, 32);
+    // two templates of <= 177 samples share a launch: every wave both templates, chunks of kMmCHPair lags; every other kernel
+    // walks chunks of kMmCH
     const bool fused = ntpl == 2 && std::max(ks0, ks1) <= kMmKS;
-    static const int fused_form = [] { const char* v = getenv("D4W_MM_FUSED"); return v ? atoi(v) : 2; }();
-    // the two-template kernel walks the rows in chunks of kMmCHPair lags, every other kernel in chunks of kMmCH
-    const int nchunk = ceil_div(ns, (fused && fused_form == 2) ? kMmCHPair : kMmCH);
-    const long long total = (long long)nx * nchunk;
+    const int nchunk = ceil_div(ns, fused ? kMmCHPair : kMmCH);
     const int per_cu = env_wgs ? env_wgs : ((ntpl == 1 && ks0 <= kMmKS) ? 3 : 2);
-    const int ncu = mm_num_cus();
-    const int grid = (int)std::min<long long>(total, (long long)ncu * per_cu);
-    // two templates of <= 177 samples: every wave both templates, two workgroups per CU (the kernel of rounds 4-6).  D4W_MM_FUSED=3:
-    // the wave-split kernel at three workgroups per CU -- built and measured in round 6, 6.32 against 6.11 ms (with the tail 6.84
-    // against 6.66): the second read of every sample fragment costs more than the third workgroup brings (profiles/r06m)
-    const int per_cu_ws = env_wgs ? env_wgs : 3;
-#define D4W_MM_LAUNCH_WS(TAIL, grid, lds, Q)                                                                                            \
-    do {                                                                                                                                \
-        if ((Q).rowmax0) D4W_LAUNCH((xcorr_mm_rows<kMmKS, 0, 3, TAIL, true, true>), dim3(grid), dim3(kMmThreads), lds, stream, Q);       \
-        else D4W_LAUNCH((xcorr_mm_rows<kMmKS, 0, 3, TAIL, false, true>), dim3(grid), dim3(kMmThreads), lds, stream, Q);                  \
-    } while (0)
-    if (tails) {
-        // whole rows per workgroup (the prefix is carried along a row): at most one workgroup per row
-        const int grid_t = (int)std::min<long long>((long long)nx, (long long)ncu * per_cu);
-        if (fused && fused_form != 2) {
-            D4W_MM_LAUNCH_WS(true, (int)std::min<long long>((long long)nx, (long long)ncu * per_cu_ws), MmGeom<kMmKS>::lds_bytes(true), P);
-            return D4W_OK;
-        }
-        if (fused) {
-            const size_t lds = MmGeom<kMmKS, kMmCHPair>::lds_bytes(true);
-            if (ks0 <= 5)
-                D4W_MM_LAUNCH_CH(5, kMmKS, 2, true, kMmCHPair, grid_t, lds, stream, P);
-            else
-                D4W_MM_LAUNCH_CH(kMmKS, kMmKS, 2, true, kMmCHPair, grid_t, lds, stream, P);
-            return D4W_OK;
-        }
-        for (int t = 0; t < ntpl; ++t) {
-            MmArgs Q = P;
-            Q.taps = taps + (size_t)t * ltaps;
-            Q.len0 = Q.len1 = t ? len1 : len0;
-            Q.tail0 = t ? (float)tail1 : (float)tail0;
-            Q.tail1 = 0.f;
-            Q.y0 = t ? y1 : y0;
-            Q.y1 = nullptr;
-            Q.rowmax0 = t ? rowmax1 : rowmax0;
-            Q.rowmax1 = nullptr;
-            const int ks = ceil_div(Q.len0 + 15, 32);
-            if (ks <= kMmKS) {
-                // (three workgroups per compute unit fit the registers only without the row maxima)
-                if (Q.rowmax0)
-                    D4W_LAUNCH((xcorr_mm_rows<kMmKS, 0, 2, true, true>), dim3(grid_t), dim3(kMmThreads), MmGeom<kMmKS>::lds_bytes(true), stream, Q);
-                else
-                    D4W_LAUNCH((xcorr_mm_rows<kMmKS, 0, 3, true, false>), dim3(grid_t), dim3(kMmThreads), MmGeom<kMmKS>::lds_bytes(true), stream, Q);
-            }
-            else if (ks <= kMmKSLong)
-                D4W_MM_LAUNCH(kMmKSLong, 0, 2, true, grid_t, MmGeom<kMmKSLong>::lds_bytes(true), stream, Q);
-            else if (ks <= 12)
-                D4W_MM_LAUNCH(12, 0, 2, true, grid_t, MmGeom<12>::lds_bytes(true), stream, Q);
-            else
-                D4W_MM_LAUNCH(kMmKSMax, 0, 2, true, grid_t, MmGeom<kMmKSMax>::lds_bytes(true), stream, Q);
-        }
-        return D4W_OK;
-    }
-    if (!fused) {
-        // one template, or a support beyond 177 samples: the templates one after the other through the one-template kernels
-        // (the Toeplitz fragments of one template alone fill the registers the fused kernel splits between two)
-        int rc = mm_one_template(P, taps, len0, y0, rowmax0, grid, stream);
-        if (rc == D4W_OK && ntpl == 2) rc = mm_one_template(P, taps + ltaps, len1, y1, rowmax1, grid, stream);
-        return rc;
-    }
-    if (fused_form != 2) {
-        D4W_MM_LAUNCH_WS(false, (int)std::min<long long>(total, (long long)ncu * per_cu_ws), MmGeom<kMmKS>::lds_bytes(false), P);
-        return D4W_OK;
-    }
-    const size_t lds = MmGeom<kMmKS, kMmCHPair>::lds_bytes(false);
-    if (ks0 <= 5)
-        D4W_MM_LAUNCH_CH(5, kMmKS, 2, false, kMmCHPair, grid, lds, stream, P);
-    else
-        D4W_MM_LAUNCH_CH(kMmKS, kMmKS, 2, false, kMmCHPair, grid, lds, stream, P);
-    return D4W_OK;
+    // with a tail a workgroup takes whole rows (the prefix is carried along a row): at most one workgroup per row; else chunks
+    const long long units = tails ? (long long)nx : (long long)nx * nchunk;
+    const int grid = (int)std::min<long long>(units, (long long)mm_num_cus() * per_cu);
+    if (fused) return tails ? mm_pair<true>(P, grid, stream) : mm_pair<false>(P, grid, stream);
+    // one template, or a support beyond 177 samples: the templates one after the other through the one-template kernels
+    // (the Toeplitz fragments of one template alone fill the registers the fused kernel splits between two)
+    int rc = mm_one_template(P, taps, len0, tails, P.tail0, y0, rowmax0, grid, stream);
+    if (rc == D4W_OK && ntpl == 2) rc = mm_one_template(P, taps + ltaps, len1, tails, P.tail1, y1, rowmax1, grid, stream);
+    return rc;
 }
 
 }  // extern "C"

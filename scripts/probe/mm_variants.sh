@@ -1,20 +1,17 @@
 #!/bin/bash
-# Probe builds of the matched filter for a same-box A/B (round 6: where the round-5 slowdown of xcorr_mm_rows comes from):
+# Probe builds of the matched filter for a same-box A/B: the phase table of xcorr_mm_rows (profiles/mm_pair/README.md, step 4) --
+# loads awaited but nothing converted, no matrix products, nothing stored.  WRONG values, timing only.  (The variants of
+# round 6 -- old split, no NaN sum, float mean, 8192-lag chunks for every kernel, dealt tail chunks, no prefix scan -- were
+# measured, profiles/r06c, r06d, r06e, and their switches removed from the kernel.)
 #   bash scripts/probe/mm_variants.sh build      (here, no GPU)
 #   bash scripts/probe/mm_variants.sh run OUT    (GPU box: every variant + the round-4 tree in _ab/r4, alternating twice)
 set -u
 cd "$(dirname "$0")/../.."
 case $1 in
 build)
-    bash scripts/probe/build_variant.sh mm_oldsplit xcorr_mm.hip -DD4W_MM_V_OLDSPLIT
-    bash scripts/probe/build_variant.sh mm_nonan xcorr_mm.hip -DD4W_MM_V_NONAN
-    bash scripts/probe/build_variant.sh mm_floatmean xcorr_mm.hip -DD4W_MM_V_FLOATMEAN
-    bash scripts/probe/build_variant.sh mm_ch8192 xcorr_mm.hip -DD4W_MM_CH=8192
-    bash scripts/probe/build_variant.sh mm_taildealt xcorr_mm.hip -DD4W_MM_V_TAIL_DEALT
-    bash scripts/probe/build_variant.sh mm_tailnoscan xcorr_mm.hip -DD4W_MM_V_TAIL_NOSCAN ;;
-build_tail)
-    bash scripts/probe/build_variant.sh mm_taildealt xcorr_mm.hip -DD4W_MM_V_TAIL_DEALT
-    bash scripts/probe/build_variant.sh mm_tailnoscan xcorr_mm.hip -DD4W_MM_V_TAIL_NOSCAN ;;
+    bash scripts/probe/build_variant.sh mm_noconv xcorr_mm.hip -DD4W_MM_V_NOCONV
+    bash scripts/probe/build_variant.sh mm_nomfma xcorr_mm.hip -DD4W_MM_V_NOMFMA
+    bash scripts/probe/build_variant.sh mm_nostore xcorr_mm.hip -DD4W_MM_V_NOSTORE ;;
 run)
     OUT=$2; mkdir -p $OUT
     fmt='
@@ -29,7 +26,7 @@ for l in sys.stdin:
 '
     for rep in 1 2; do
         (cd _ab/r4 && timeout 300 python scripts/time_xcorr_mm.py 2>/dev/null | python -c "$fmt" "r4        rep $rep")
-        for tag in ${TAGS:-base mm_oldsplit mm_nonan mm_floatmean mm_ch8192 mm_taildealt mm_tailnoscan}; do
+        for tag in ${TAGS:-base mm_noconv mm_nomfma mm_nostore}; do
             lib=$PWD/das4whales_amd/lib/probe/libd4w_$tag.so
             [ $tag = base ] && lib=$PWD/das4whales_amd/lib/libd4w.so
             [ -f $lib ] || continue

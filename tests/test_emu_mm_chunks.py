@@ -143,3 +143,36 @@ def test_row_maxima_and_a_row_with_nan(emu, with_tail):
         assert np.isnan(rm[t][2]) and np.isnan(ys[t][2]).any()
         keep = [0, 1, 3, 4]
         assert np.array_equal(rm[t][keep], plain[t][keep].max(axis=1)) and np.array_equal(ys[t][keep], plain[t][keep])
+
+
+@pytest.mark.parametrize("support", [150, 200, 330, 450])
+def test_one_template_kernels_of_every_depth_with_tail_and_row_maxima(emu, support):
+    """One template of 6, 7, 11 and 15 k-steps -- the 6-, 8-, 12- and 16-step kernels -- without and with the tail, without and
+    with the row maxima (the 6-step kernel with both is an instantiation of its own): float64, the same values whether or not
+    the maxima are formed, and the maxima of what was stored.  One sample into a third chunk of 4096 lags."""
+    nx, ns = 5, 8193
+    x = cs.rows(nx, ns, seed=300 + support)
+    for with_tail in (False, True):
+        tpl = cs.template(ns, support, zero_mean=not with_tail, seed=support)
+        taps, tail = cs.taps_and_tail(tpl, with_tail)
+        (plain,) = run(emu, x, [taps], [tail])
+        e = cs.row_err(plain, cs.reference(x, tpl, with_tail))
+        print("support %d %s: worst row %.2e" % (support, "tail" if with_tail else "tail0", e.max()))
+        assert e.max() < TOL, e
+        ys, rm = run(emu, x, [taps], [tail], want_max=True)
+        assert np.array_equal(ys[0], plain) and np.array_equal(rm[0], plain.max(axis=1))
+
+
+@pytest.mark.parametrize("with_tail", [False, True], ids=["tail0", "tail"])
+def test_row_maxima_of_the_pair_of_six_and_six_steps(emu, with_tail):
+    """The two-template kernel of 6 + 6 k-steps (supports 163 / 150) with the row maxima."""
+    nx, ns = 5, 8193
+    x = cs.rows(nx, ns, seed=98)
+    tpls = [cs.template(ns, s, zero_mean=not with_tail, seed=s) for s in cs.SUPPORTS[1]]
+    tt = [cs.taps_and_tail(tp, with_tail) for tp in tpls]
+    taps, tails = [a for a, _ in tt], [b for _, b in tt]
+    plain = run(emu, x, taps, tails)
+    ys, rm = run(emu, x, taps, tails, want_max=True)
+    for t in range(2):
+        assert cs.row_err(plain[t], cs.reference(x, tpls[t], with_tail)).max() < TOL
+        assert np.array_equal(ys[t], plain[t]) and np.array_equal(rm[t], plain[t].max(axis=1))

@@ -120,3 +120,51 @@ def test_unaligned_rows_short_continuation_and_row_maxima(dw):
     keep = torch.tensor([0, 1, 3, nx - 1], device="cuda")
     for t in range(2):
         assert bool(torch.isnan(rm[t][2])) and torch.equal(rm[t][keep], base[t][keep].max(dim=1).values)
+
+
+def _checked(nx):
+    return np.unique(np.r_[np.arange(min(nx, CHECKED)), np.arange(max(nx - CHECKED, 0), nx)])
+
+
+@pytest.mark.parametrize("support", [150, 200, 330, 450])
+def test_one_template_kernels_of_every_depth_with_tail_and_row_maxima(dw, support):
+    """One template of 6, 7, 11 and 15 k-steps -- the 6-, 8-, 12- and 16-step kernels -- without and with the tail, without and
+    with the row maxima (the 6-step kernel with both is an instantiation of its own): float64, the same values whether or not
+    the maxima are formed, and the maxima of what was stored.  One row more than the grid, one sample into a third chunk."""
+    nx, ns = 513, 8193
+    x = cs.rows(nx, ns, seed=300 + support)
+    kinds, sel = cs.kinds(nx), _checked(nx)
+    xd = torch.from_numpy(x).cuda()
+    for with_tail in (False, True):
+        tpl = cs.template(ns, support, zero_mean=False, seed=support)
+        taps, tail = cs.taps_and_tail(tpl, with_tail)
+        tails = [tail] if with_tail else None
+        (plain,) = dw.detect._xcorr_device(xd, [taps], normalize=True, method="mm", tails=tails)
+        e = cs.row_err(plain[sel].cpu().numpy(), cs.reference(x[sel], tpl, with_tail))
+        print("support %d tail %s: worst white row %.2e, worst other row %.2e" % (
+            support, with_tail, max([v for v, r in zip(e, sel) if kinds[r] == "white"], default=0.0),
+            max([v for v, r in zip(e, sel) if kinds[r] != "white"], default=0.0)))
+        assert np.all(e < bounds([kinds[r] for r in sel])), (with_tail, e)
+        rm = []
+        (y,) = dw.detect._xcorr_device(xd, [taps], normalize=True, method="mm", tails=tails, row_max=rm)
+        assert torch.equal(y, plain) and torch.equal(rm[0], plain.max(dim=1).values)
+
+
+@pytest.mark.parametrize("with_tail", [False, True], ids=["tail0", "tail"])
+def test_row_maxima_of_the_pairs(dw, with_tail):
+    """The two-template kernels of 5 + 6 and of 6 + 6 k-steps with the row maxima, without and with the tail."""
+    nx, ns = 513, 8193
+    x = cs.rows(nx, ns, seed=98)
+    kinds, sel = cs.kinds(nx), _checked(nx)
+    xd = torch.from_numpy(x).cuda()
+    for sup in cs.SUPPORTS:
+        tpls = [cs.template(ns, s, zero_mean=False, seed=s) for s in sup]
+        tt = [cs.taps_and_tail(tp, with_tail) for tp in tpls]
+        taps, tails = [a for a, _ in tt], ([b for _, b in tt] if with_tail else None)
+        plain = dw.detect._xcorr_device(xd, taps, normalize=True, method="mm", tails=tails)
+        rm = []
+        ys = dw.detect._xcorr_device(xd, taps, normalize=True, method="mm", tails=tails, row_max=rm)
+        for t in range(2):
+            e = cs.row_err(plain[t][sel].cpu().numpy(), cs.reference(x[sel], tpls[t], with_tail))
+            assert np.all(e < bounds([kinds[r] for r in sel])), (sup, t, e)
+            assert torch.equal(ys[t], plain[t]) and torch.equal(rm[t], plain[t].max(dim=1).values)
