@@ -180,6 +180,14 @@ def _load():
         "d4w_loc_misfit_grid_f64": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_double, c_void_p, c_int, c_void_p, c_int,
                                             ctypes.c_double, c_void_p, c_void_p, c_void_p]),
         "d4w_loc_arrival_times_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p]),
+        "d4w_assoc_vote_i32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, ctypes.c_double, ctypes.c_double,
+                                       c_void_p, c_int, c_void_p, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,
+                                       c_void_p, c_void_p, c_void_p]),
+        "d4w_assoc_best_ws_bytes": (ctypes.c_size_t, []),
+        "d4w_assoc_best_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "d4w_assoc_select_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_int,
+                                         c_void_p, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch: fail loudly

@@ -2,8 +2,9 @@
 
 The nine reference functions keep their names, parameter names and defaults.  The Gauss-Newton solver, the travel times and
 the misfit grid run in csrc/loc.hip (float64); `solve_lq_batch`, `misfit_grid` and `first_guess_grid` are the batched forms
-the reference does not have.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the same device and
-stream.  The four small per-channel helpers (distances, radii, angles) are host float64 arithmetic for NumPy input, like the
+the reference does not have; `vote_grid` and `associate_picks` (csrc/assoc.hip) turn the picks of detect.pick_times* into
+the [ncalls x channel] arrival times these take.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
+same device and stream.  The four small per-channel helpers (distances, radii, angles) are host float64 arithmetic for NumPy input, like the
 index arithmetic of the other namespaces; for tensors they stay on the device.
 
 Arrival times that are NaN mean "no pick on this channel": the solver and the grid skip them (the reference has no such
@@ -303,3 +304,184 @@ def first_guess_grid(Ti, cable_pos, c0, xs, ys, z):
                        t0.reshape(ncalls, -1).gather(1, k[:, None])[:, 0]], dim=1)
     out[torch.isnan(out[:, 3])] = float("nan")
     return _back(out[0] if single else out, Ti, cable_pos)
+
+
+# ------------------------------------------------------------------------------------------
+# beyond the reference: association of picks into calls (csrc/assoc.hip)
+# ------------------------------------------------------------------------------------------
+def _pick_table(picks, nch, device):
+    """The picks as (packed [2 x K] int64 on the device ordered by (channel, sample), counts [nch] int32 on the device,
+    order, device output?).  order: None, or the positions in the caller's table of the rows of `packed`.  A PickRows
+    stays on the device; every other form is a small host table, checked and sorted there."""
+    from .detect import PickRows, convert_pick_times
+    if isinstance(picks, PickRows):
+        packed, counts = picks.packed, picks.counts.to(torch.int32)
+        if counts.numel() > nch:
+            raise ValueError("the picks cover %d channels, cable_pos has %d" % (counts.numel(), nch))
+        if counts.numel() < nch:
+            counts = torch.cat([counts, counts.new_zeros(nch - counts.numel())])
+        return packed.contiguous(), counts.contiguous(), None, True
+    on_device = dev.is_tensor(picks) or (isinstance(picks, tuple) and any(dev.is_tensor(p) for p in picks))
+    if isinstance(picks, tuple) and len(picks) == 2:                      # what select_picked_times returns
+        picks = [p.cpu().numpy() if dev.is_tensor(p) else np.asarray(p) for p in picks]
+        tab = np.stack([np.asarray(p).reshape(-1) for p in picks]) if len(picks[0]) else np.zeros((2, 0))
+    elif dev.is_tensor(picks):
+        tab = picks.cpu().numpy()
+    elif isinstance(picks, np.ndarray) and picks.dtype != object:
+        tab = picks
+    else:                                                                  # a ragged list of per-channel index arrays
+        if len(picks) > nch:
+            raise ValueError("the picks cover %d channels, cable_pos has %d" % (len(picks), nch))
+        tab = convert_pick_times([p.cpu().numpy() if dev.is_tensor(p) else p for p in picks])
+    if tab.ndim != 2 or tab.shape[0] != 2:
+        raise ValueError("picks must be a PickRows, a 2 x K table (channel, sample), that pair as a tuple, or a list of "
+                         "per-channel index arrays; got an array of shape %s" % (tuple(tab.shape),))
+    if tab.size and tab.dtype.kind not in "iu":
+        raise ValueError("the pick table must hold integers (channel and sample indices), got %s" % tab.dtype)
+    tab = tab.astype(np.int64)
+    if tab.shape[1] and (tab[0].min() < 0 or tab[0].max() >= nch):
+        raise ValueError("channel indices must lie within 0 .. %d" % (nch - 1))
+    order = None
+    key = tab[0] * (1 << 40) + tab[1] if tab.shape[1] and np.abs(tab[1]).max() < (1 << 40) else None
+    if tab.shape[1] > 1 and (key is None or np.any(np.diff(key) < 0)):
+        order = np.lexsort((tab[1], tab[0]))                               # stable: equal picks keep the caller's order
+        tab = tab[:, order]
+    counts = np.bincount(tab[0], minlength=nch).astype(np.int32)
+    d = device or ("cuda:%d" % torch.cuda.current_device())
+    return (torch.from_numpy(np.ascontiguousarray(tab)).to(d), torch.from_numpy(counts).to(d), order, on_device)
+
+
+def _assoc_range(packed, fs, cable, c0, gx, gy, z, dt, t0_range):
+    """(lo, nbins, edges as float64 ndarray).  The default range reads the table's extreme samples and the small arrays on the
+    host: lo = min t - Dmax / c0, hi = max t, Dmax = the largest distance between the 8 corners of the cable's bounding box
+    and the 4 corners of the grid rectangle at depth z.  Without picks the default takes min t = max t = 0."""
+    if not (np.isfinite(dt) and dt > 0 and np.isfinite(fs) and fs > 0 and np.isfinite(c0) and c0 > 0):
+        raise ValueError("dt, fs and c0 must be positive and finite")
+    if t0_range is not None:
+        lo, hi = (float(v) for v in t0_range)
+    else:
+        if packed.shape[1]:
+            imin, imax = (int(v) for v in torch.stack(torch.aminmax(packed[1])).cpu())
+        else:
+            imin = imax = 0
+        c, x, y = cable.cpu().numpy(), gx.cpu().numpy(), gy.cpu().numpy()
+        dmax = 0.0
+        for cx in (c[:, 0].min(), c[:, 0].max()):
+            for cy in (c[:, 1].min(), c[:, 1].max()):
+                for cz in (c[:, 2].min(), c[:, 2].max()):
+                    for px in (x.min(), x.max()):
+                        for py in (y.min(), y.max()):
+                            dmax = max(dmax, float(np.sqrt((cx - px) ** 2 + (cy - py) ** 2 + (cz - z) ** 2)))
+        lo, hi = imin / fs - dmax / c0, imax / fs
+    if not (np.isfinite(lo) and np.isfinite(hi) and hi >= lo):
+        raise ValueError("t0_range must be finite with lo <= hi")
+    nbins = int(np.ceil((hi - lo) / dt)) + 1
+    if nbins < 2:
+        raise ValueError("the emission-time range [%g, %g] gives %d bin of %g s; the pair score needs two" % (lo, hi, nbins, dt))
+    return lo, nbins, lo + dt * np.arange(nbins + 1)
+
+
+def _assoc_setup(picks, fs, cable_pos, c0, xs, ys, z, dt, t0_range):
+    device = picks.counts.device if hasattr(picks, "counts") else _device_of(picks, cable_pos, xs, ys)
+    cable = _cable(cable_pos, device)
+    gx, gy = _f64(xs, cable.device).reshape(-1), _f64(ys, cable.device).reshape(-1)
+    if gx.numel() < 1 or gy.numel() < 1:
+        raise ValueError("the grid needs at least one node")
+    fs, c0, z, dt = float(fs), float(c0), float(z), float(dt)
+    packed, counts, order, on_device = _pick_table(picks, cable.shape[0], cable.device)
+    lo, nbins, edges = _assoc_range(packed, fs, cable, c0, gx, gy, z, dt, t0_range)
+    as_tensor = on_device or any(dev.is_tensor(a) for a in (cable_pos, xs, ys))
+    return cable, gx, gy, fs, c0, z, dt, packed, counts, order, lo, nbins, edges, as_tensor
+
+
+def _vote(packed, idx, sign, accumulate, cable, fs, c0, gx, gy, z, lo, dt, nbins, votes, stop):
+    K = packed.shape[1]
+    _lib.check(_lib.lib.d4w_assoc_vote_i32(dev.ptr(packed) if K else None, K, dev.ptr(idx) if idx is not None else None,
+                                           idx.numel() if idx is not None else 0, sign, accumulate, dev.ptr(cable), cable.shape[0],
+                                           fs, c0, dev.ptr(gx), gx.numel(), dev.ptr(gy), gy.numel(), z, lo, dt, nbins,
+                                           dev.out_ptr(votes), dev.ptr(stop) if stop is not None else None, dev.stream_ptr(cable)))
+
+
+def _out(y, as_tensor):
+    return y if as_tensor else y.cpu().numpy()
+
+
+def vote_grid(picks, fs, cable_pos, c0, xs, ys, z, dt, t0_range=None):
+    """Delay-and-vote of picks over the nodes (xs[ix], ys[iy], z): votes[iy, ix, b] counts the picks (channel ch, sample i)
+    whose emission time e = i / fs - |cable_pos[ch] - node| / c0 falls into bin b = floor((e - lo) / dt); the picks of one
+    call pile up in one bin at the node nearest its source.  Returns (votes [ny x nx x nbins] int32, edges [nbins + 1]
+    float64 = lo + dt arange(nbins + 1)).
+
+    picks: a detect.PickRows (stays on the device), a 2 x K integer table (channel, sample) as detect.convert_pick_times
+    returns, the tuple detect.select_picked_times returns, or a list of per-channel index arrays.  t0_range = (lo, hi) sets
+    the emission times covered; None: lo = earliest pick - Dmax / c0, hi = latest pick, Dmax the largest distance between
+    the corners of the cable's bounding box and of the grid.  nbins = ceil((hi - lo) / dt) + 1.  Picks whose bin falls
+    outside are not counted.  NumPy in -> NumPy out; a CUDA tensor or PickRows in -> tensors on that device."""
+    cable, gx, gy, fs, c0, z, dt, packed, counts, order, lo, nbins, edges, as_tensor = _assoc_setup(picks, fs, cable_pos, c0, xs, ys, z,
+                                                                                                  dt, t0_range)
+    with torch.cuda.device(cable.device):
+        votes = torch.empty((gy.numel(), gx.numel(), nbins), dtype=torch.int32, device=cable.device)
+        _vote(packed, None, 1, 0, cable, fs, c0, gx, gy, z, lo, dt, nbins, votes, None)
+    return _out(votes, as_tensor), (torch.from_numpy(edges).to(cable.device) if as_tensor else edges)
+
+
+def associate_picks(picks, fs, cable_pos, c0, xs, ys, z, dt, min_picks, max_calls=64, t0_range=None, return_votes=False):
+    """Group picks into calls by a greedy delay-and-vote over the nodes (xs[ix], ys[iy], z); see vote_grid for `picks`, the
+    bins and `t0_range`.  Up to `max_calls` rounds:
+      1. the node g* and bin b* of the largest pair score votes[g][b] + votes[g][b + 1] (ties: the smallest flat index
+         g (nbins - 1) + b); stop when it is below `min_picks`;
+      2. per channel, of its unassigned picks in bins b*, b* + 1 at g*, the one whose emission time is nearest the window
+         centre lo + (b* + 1) dt (ties: the earlier row of the table) becomes the call's arrival time on that channel;
+      3. the chosen picks' votes are taken off every node.
+    Returns (Ti [ncalls x channel] float64 with NaN = no pick, what solve_lq_batch takes; info) with info a dict of
+      first_guess [ncalls x 4]  x, y, z of the node and the mean emission time of the chosen picks: solve_lq_batch's first_guess
+      node, bin, score, npicks [ncalls] int32: flat node index iy nx + ix, b*, the pair score, channels chosen
+      assigned [K] int32       per pick, in the caller's order: the call it went to, 1-based; 0 = none
+      edges [nbins + 1]        bin edges of the emission time
+      votes [ny x nx x nbins]  with return_votes: the accumulator after the last round = vote_grid of the unassigned picks
+    All rounds are enqueued at once; the call synchronises with the host once, for the number of calls found (and, with
+    t0_range = None, once before the first round for the extreme pick times)."""
+    if int(min_picks) < 1:
+        raise ValueError("min_picks must be at least 1")
+    if int(max_calls) < 0:
+        raise ValueError("max_calls must not be negative")
+    min_picks, max_calls = int(min_picks), int(max_calls)
+    cable, gx, gy, fs, c0, z, dt, packed, counts, order, lo, nbins, edges, as_tensor = _assoc_setup(picks, fs, cable_pos, c0, xs, ys, z,
+                                                                                                  dt, t0_range)
+    d, nch, K = cable.device, cable.shape[0], packed.shape[1]
+    nx, ny = gx.numel(), gy.numel()
+    lib = _lib.lib
+    with torch.cuda.device(d):
+        stream = dev.stream_ptr(cable)
+        votes = torch.empty((ny, nx, nbins), dtype=torch.int32, device=d)
+        Ti = torch.empty((max_calls, nch), dtype=torch.float64, device=d)
+        fg = torch.empty((max_calls, 4), dtype=torch.float64, device=d)
+        rec = torch.zeros((max_calls, 4), dtype=torch.int32, device=d)
+        state = torch.zeros(2, dtype=torch.int32, device=d)
+        assigned = torch.zeros(K, dtype=torch.int32, device=d)
+        chosen = torch.empty(nch, dtype=torch.int32, device=d)
+        e_chosen = torch.empty(nch, dtype=torch.float64, device=d)
+        off = torch.empty(nch, dtype=torch.int64, device=d)
+        summ = torch.empty(2, dtype=torch.int64, device=d)
+        ws = torch.empty(lib.d4w_assoc_best_ws_bytes(), dtype=torch.uint8, device=d)
+        _lib.check(lib.d4w_pick_offsets_i64(dev.ptr(counts), nch, dev.out_ptr(off), dev.out_ptr(summ), stream))
+        _vote(packed, None, 1, 0, cable, fs, c0, gx, gy, z, lo, dt, nbins, votes, None)
+        for c in range(max_calls if K else 0):                   # no host synchronisation and no torch kernel in here
+            _lib.check(lib.d4w_assoc_best_i32(dev.ptr(votes), nx, ny, nbins, min_picks, c, dev.out_ptr(state), dev.out_ptr(rec),
+                                              dev.out_ptr(ws), stream))
+            _lib.check(lib.d4w_assoc_select_f64(dev.ptr(packed), K, dev.ptr(off), dev.ptr(cable), nch, fs, c0, dev.ptr(gx), nx,
+                                                dev.ptr(gy), ny, z, lo, dt, nbins, c, dev.ptr(state), dev.out_ptr(rec),
+                                                dev.out_ptr(assigned), dev.out_ptr(Ti), dev.out_ptr(chosen), dev.out_ptr(e_chosen),
+                                                dev.out_ptr(fg), stream))
+            _vote(packed, chosen, -1, 1, cable, fs, c0, gx, gy, z, lo, dt, nbins, votes, state)
+        ncalls = int(state[1].item()) if K and max_calls else 0  # the call's one host read
+        if order is not None:
+            inv = torch.empty(K, dtype=torch.int64, device=d)
+            inv[torch.from_numpy(order).to(d)] = torch.arange(K, dtype=torch.int64, device=d)
+            assigned = assigned[inv]                             # row j of the caller's table is row inv[j] of the sorted one
+    info = {"first_guess": fg[:ncalls], "node": rec[:ncalls, 0].contiguous(), "bin": rec[:ncalls, 1].contiguous(),
+            "score": rec[:ncalls, 2].contiguous(), "npicks": rec[:ncalls, 3].contiguous(), "assigned": assigned,
+            "edges": torch.from_numpy(edges).to(d)}
+    if return_votes:
+        info["votes"] = votes
+    return _out(Ti[:ncalls], as_tensor), {k: _out(v, as_tensor) for k, v in info.items()}

@@ -683,6 +683,53 @@ int d4w_loc_misfit_grid_f64(const double* cable_pos, int nch, const double* Ti, 
 int d4w_loc_arrival_times_f64(const double* cable_pos, int nch, const double* pos, const double* t0, int npos, double c0,
                               double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Association of picks into calls (das4whales_amd/csrc/assoc.hip): a delay-and-vote over a position grid, the step
+ * between detect.pick_times* and the localisation above (the reference has none).  float64 arithmetic, int32 votes; every
+ * pointer is DEVICE memory.  Votes are integers, so every result is run-to-run bit-identical.
+ *
+ *   picks [2][npicks] int64: row 0 = channel ch_k (0 <= ch_k < nch), row 1 = sample i_k, ordered by (channel, sample) --
+ *     the packed table of d4w_pack_picks_i64; t_k = i_k / fs.  npicks <= 2^30; npicks = 0 is valid (picks may be NULL).
+ *   node g = iy nx + ix at (xs[ix], ys[iy], z), the layout of d4w_loc_misfit_grid_f64.
+ *   e_kg = t_k - |cable_pos[ch_k] - node_g| / c0                  emission time of pick k if it came from node g
+ *   bin(k, g) = floor((e_kg - lo) / dt)                           (evaluated as (e_kg - lo) * (1 / dt), |..| * (1 / c0))
+ *   votes[g][b] = #{k : bin(k, g) = b}, 0 <= b < nbins            picks whose bin falls outside are not counted
+ *   s[g][b] = votes[g][b] + votes[g][b + 1], 0 <= b < nbins - 1   a call astride a bin edge is not split
+ *
+ * d4w_assoc_vote_i32: votes [ny nx][nbins] = sign * count (accumulate = 0) or += sign * count (accumulate != 0), counted over
+ *   all picks (idx = NULL) or over the picks idx[0 .. nidx - 1] (int32 positions in the table, entries < 0 are skipped:
+ *   the `chosen` list of d4w_assoc_select_f64, read in place).  sign = +1 or -1.  stop = NULL, or a DEVICE int32 that makes
+ *   the launch return at once when non-zero (state of d4w_assoc_best_i32).  No global atomics: every element of votes is
+ *   written by one workgroup.  nbins above the 1024-bin LDS tile runs one pass over the picks per 1024 bins.
+ * d4w_assoc_best_i32: (g*, b*) = arg-max of s, ties to the smallest flat index g (nbins - 1) + b.  state = int32 [2] =
+ *   {stop, calls found}, zeroed by the caller before the first round.  If state[0] != 0 nothing happens.  If
+ *   s[g*][b*] < min_picks: state[0] = 1.  Else rec[call][0 .. 3] = {g*, b*, s[g*][b*], 0} and state[1] = call + 1.
+ *   rec = int32 [calls][4]; ws = DEVICE scratch of d4w_assoc_best_ws_bytes() bytes.
+ * d4w_assoc_select_f64: for round `call` (nothing happens if state[0] != 0), with (g*, b*) = rec[call][0 .. 1] and the window
+ *   centre ec = lo + (b* + 1) dt: per channel, among its picks k with assigned[k] = 0 and bin(k, g*) in {b*, b* + 1}, the one
+ *   of smallest |e_kg* - ec|, ties to the smaller k.  offsets [nch] int64 = inclusive prefix sum of the picks per channel
+ *   (d4w_pick_offsets_i64): channel c owns picks offsets[c - 1] .. offsets[c] - 1.  Writes Ti[call][c] = t_k (NaN: none),
+ *   chosen[c] = k (-1: none), e_chosen[c] = e_kg* (NaN: none), assigned[k] = call + 1; then rec[call][3] = channels chosen
+ *   and first_guess[call] = {xs[ix*], ys[iy*], z, mean of e_chosen over the chosen channels} (the form d4w_loc_solve_f64
+ *   takes).  Ti = [calls][nch], chosen = int32 [nch], e_chosen = [nch], assigned = int32 [npicks], first_guess = [calls][4].
+ *
+ * One greedy round is best, select, vote(idx = chosen, sign = -1, accumulate = 1, stop = state): afterwards votes is the vote
+ * of the picks with assigned = 0 counted from scratch.  All rounds can be enqueued without a host synchronisation; state[1]
+ * is then the number of calls.
+ * Errors: D4W_EINVAL for nch < 1, nx < 1, ny < 1, nbins < 2, dt, fs or c0 not finite or <= 0, sign other than +1 / -1,
+ *   a NULL required pointer, npicks or call < 0.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_assoc_vote_i32(const int64_t* picks, int npicks, const int32_t* idx, int nidx, int sign, int accumulate,
+                       const double* cable_pos, int nch, double fs, double c0, const double* xs, int nx, const double* ys, int ny,
+                       double z, double lo, double dt, int nbins, int32_t* votes, const int32_t* stop, void* stream);
+size_t d4w_assoc_best_ws_bytes(void);
+int d4w_assoc_best_i32(const int32_t* votes, int nx, int ny, int nbins, int min_picks, int call, int32_t* state, int32_t* rec,
+                       void* ws, void* stream);
+int d4w_assoc_select_f64(const int64_t* picks, int npicks, const int64_t* offsets, const double* cable_pos, int nch, double fs,
+                         double c0, const double* xs, int nx, const double* ys, int ny, double z, double lo, double dt, int nbins,
+                         int call, const int32_t* state, int32_t* rec, int32_t* assigned, double* Ti, int32_t* chosen,
+                         double* e_chosen, double* first_guess, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
