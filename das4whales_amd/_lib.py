@@ -141,6 +141,15 @@ def _load():
         "d4w_welch_supported": (c_int, [c_int]),
         "d4w_welch_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
         "d4w_chunk_energy_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+        "d4w_resample_max_taps": (c_int, []),
+        "d4w_resample_out_len": (c_int, [c_int, c_int, c_int]),
+        "d4w_resample_reach": (c_int, [c_int, c_int, c_int, P(c_int), P(c_int)]),
+        "d4w_resample_f32": (c_int, [c_void_p, ctypes.c_size_t, c_int, c_int, c_void_p, ctypes.c_size_t, c_int, c_void_p,
+                                     ctypes.c_size_t, c_int, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_double,
+                                     ctypes.c_double, c_int, c_void_p, c_void_p]),
+        "d4w_resample_raw_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                                         ctypes.c_double, c_void_p, c_void_p]),
+        "d4w_raw_row_mean_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
         "d4w_stft_frames": (c_int, [c_int, c_int]),
         "d4w_stft_mag_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
         "d4w_stft_mm_eligible": (c_int, [c_int, c_int, c_int, c_int]),

@@ -26,15 +26,22 @@ def _to_device_raw(raw, device=None):
     return t.contiguous()
 
 
-def load_das_data_array(raw_data, selected_channels, metadata):
+def load_das_data_array(raw_data, selected_channels, metadata, decimate=None):
     """The array part of load_das_data (data_handle.py:181-230): rows
     selected_channels[0]:selected_channels[1]:selected_channels[2] of the raw [channel x time]
     matrix as strain (float32 CUDA tensor), plus the time and distance axes.  raw_data may be a NumPy
-    array (int32 / int16 / float) or a torch tensor; the raw matrix crosses PCIe in its native width."""
+    array (int32 / int16 / float) or a torch tensor; the raw matrix crosses PCIe in its native width.
+
+    decimate=q (an integer > 1) for a file that does not arrive at the working rate: the strain is low-passed and every
+    q-th sample kept (dsp.decimate's taps) as the raw rows are read -- each row once for its float64 mean and once by the
+    resampler, the full-rate float32 block is never written.  The strain is [nx, ceil(ns / q)], tx = arange(n_out) q / fs;
+    `metadata` is not modified: the caller's sampling rate is now metadata['fs'] / q."""
     t = _to_device_raw(raw_data)
     nch, ns = t.shape
     c0, c1, step = int(selected_channels[0]), min(int(selected_channels[1]), nch), int(selected_channels[2])
     nx = len(range(c0, c1, step))
+    if decimate is not None and int(decimate) != 1:
+        return _load_decimated(t, c0, step, nx, metadata, decimate)
     y = torch.empty((nx, ns), dtype=torch.float32, device=t.device)
     with torch.cuda.device(t.device):
         check(lib.d4w_raw2strain_f32(dev.ptr(t), _DTYPES[t.dtype], ns, c0, step, nx, float(metadata["scale_factor"]),
@@ -42,6 +49,26 @@ def load_das_data_array(raw_data, selected_channels, metadata):
         # the kernel runs on torch's current stream, the stream a temporary `t` was allocated on: the caching allocator
         # re-uses its memory in stream order, no host synchronisation needed (a resident raw file keeps the pipeline asynchronous)
     tx = np.arange(ns) / metadata["fs"]                                          # data_handle.py:227
+    dist = (np.arange(nx) * step + c0) * metadata["dx"]                          # data_handle.py:228
+    return y, tx, dist
+
+
+def _load_decimated(t, c0, step, nx, metadata, q):
+    """load_das_data_array(decimate=q) of the raw device matrix t: d4w_raw_row_mean_f64, then d4w_resample_raw_f32."""
+    from . import dsp
+    if int(q) != q or q < 1:
+        raise ValueError("decimate must be an integer >= 1")
+    q = int(q)
+    ns = t.shape[1]
+    h = dsp._decimate_taps(q)
+    taps = dsp._taps_on_device(1, q, h, t.device)
+    mean = torch.empty(nx, dtype=torch.float64, device=t.device)
+    y = torch.empty((nx, -(-ns // q)), dtype=torch.float32, device=t.device)
+    with torch.cuda.device(t.device):
+        check(lib.d4w_raw_row_mean_f64(dev.ptr(t), _DTYPES[t.dtype], ns, c0, step, nx, dev.ptr(mean), dev.stream_ptr(t)))
+        check(lib.d4w_resample_raw_f32(dev.ptr(t), _DTYPES[t.dtype], ns, c0, step, nx, dev.ptr(taps), int(h.size), 1, q,
+                                       dev.ptr(mean), float(metadata["scale_factor"]), dev.ptr(y), dev.stream_ptr(t)))
+    tx = np.arange(y.shape[1]) * q / metadata["fs"]
     dist = (np.arange(nx) * step + c0) * metadata["dx"]                          # data_handle.py:228
     return y, tx, dist
 
@@ -119,9 +146,9 @@ class PinnedIngest:
         torch.cuda.current_stream(self.device).wait_event(self._ready[slot])
         return self._dev[slot]
 
-    def strain(self, slot, selected_channels, metadata):
-        """load_das_data_array of the uploaded slot: (strain float32 CUDA tensor, tx, dist)."""
-        out = load_das_data_array(self.raw(slot), selected_channels, metadata)
+    def strain(self, slot, selected_channels, metadata, decimate=None):
+        """load_das_data_array of the uploaded slot: (strain float32 CUDA tensor, tx, dist); decimate=q as there."""
+        out = load_das_data_array(self.raw(slot), selected_channels, metadata, decimate=decimate)
         self._free[slot].record(torch.cuda.current_stream(self.device))
         self._consumed[slot] = True
         return out

@@ -1127,6 +1127,158 @@ def welch_psd(trace, fs, nperseg=1024, noverlap=None, chunk=None):
     return f, dev.like_input(pxx[0] if was1d else pxx, trace)
 
 
+# ---------------------------------------------------------------------------------------------
+# polyphase resampling / FIR decimation (csrc/resample.hip)
+# ---------------------------------------------------------------------------------------------
+_RESAMPLE_PADTYPES = ("constant", "mean")
+_resample_taps_dev = {}           # (device index, up, down, taps as bytes) -> float32 taps on the device
+
+
+def _resample_taps(up, down, window):
+    """(up, down, h): the rates reduced by their gcd and resample_poly's float64 taps, already multiplied by up
+    (scipy/signal/_signaltools.py resample_poly: firwin(20 max(up, down) + 1, 1 / max(up, down), window) unless `window`
+    is the taps themselves)."""
+    import math
+    import scipy.signal as sp
+    if int(up) != up or int(down) != down or up < 1 or down < 1:
+        raise ValueError("up and down must be integers >= 1")
+    up, down = int(up), int(down)
+    g = math.gcd(up, down)
+    up, down = up // g, down // g
+    if isinstance(window, (list, np.ndarray)):
+        h = np.array(window, dtype=np.float64)
+        if h.ndim != 1 or h.size < 1:
+            raise ValueError("window must be a 1-D array of at least one tap")
+    elif up == down:
+        h = np.ones(1)                              # a copy: SciPy designs nothing either
+    else:
+        m = max(up, down)
+        h = sp.firwin(20 * m + 1, 1.0 / m, window=window)
+    return up, down, h * up
+
+
+def _decimate_taps(q, n=None):
+    """scipy.signal.decimate(ftype='fir')'s taps: firwin(n + 1, 1 / q, window='hamming'), n = 20 q by default."""
+    import scipy.signal as sp
+    if int(q) != q or q < 1:
+        raise ValueError("q must be an integer >= 1")
+    n = 20 * int(q) if n is None else int(n)
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    return sp.firwin(n + 1, 1.0 / int(q), window="hamming")
+
+
+def _taps_on_device(up, down, h, device):
+    """The taps rounded to float32 once, on `device` (kept: the second call with the same taps uploads nothing)."""
+    if h.size > lib.d4w_resample_max_taps():
+        raise ValueError("d4w: %d taps: at most %d (designed taps: max(up, down) <= %d)"
+                         % (h.size, lib.d4w_resample_max_taps(), (lib.d4w_resample_max_taps() - 1) // 20))
+    device = torch.device(device)
+    h32 = np.ascontiguousarray(h, dtype=np.float32)
+    key = (device.index, up, down, h32.tobytes())
+    t = _resample_taps_dev.get(key)
+    if t is None:
+        if len(_resample_taps_dev) >= 32:
+            _resample_taps_dev.clear()
+        t = _resample_taps_dev[key] = torch.from_numpy(h32).to(device)
+    return t
+
+
+def _rows_with_pitch(x):
+    """float32 CUDA rows of a [nx, ns] input and their distance in floats: a row subset of a resident block (x[a:b:s]) is
+    read in place, anything else goes through to_device_f32."""
+    if dev.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0 \
+            and x.stride(1) == 1 and (x.shape[0] == 1 or x.stride(0) >= x.shape[1]):
+        return x, (x.stride(0) if x.shape[0] > 1 else x.shape[1])
+    x = dev.to_device_f32(x)
+    return x, x.shape[1]
+
+
+def _neighbour(block, nx, was1d, device, name):
+    if block is None:
+        return None, 0, 0
+    if was1d and getattr(block, "ndim", 0) == 1:
+        block = block[None, :]
+    if getattr(block, "ndim", 0) != 2 or block.shape[0] != nx:
+        raise ValueError("%s must hold the samples next to every row: [%d, n]" % (name, nx))
+    if block.shape[1] == 0:
+        return None, 0, 0
+    b, ld = _rows_with_pitch(block if not dev.is_tensor(block) or block.is_cuda else block.to(device))
+    return b, ld, b.shape[1]
+
+
+def resample_reach(up, down, window=('kaiser', 5.0)):
+    """(n_left, n_right): the samples before and after a file that resample_poly(., up, down, window=window) reaches --
+    what prev_tail / next_head must hold for the file to continue its neighbours exactly."""
+    up, down, h = _resample_taps(up, down, window)
+    nl, nr = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.d4w_resample_reach(int(h.size), up, down, ctypes.byref(nl), ctypes.byref(nr)))
+    return nl.value, nr.value
+
+
+def resample_poly(trace, up, down, axis=-1, window=('kaiser', 5.0), padtype='constant', cval=None, *,
+                  prev_tail=None, next_head=None):
+    """scipy.signal.resample_poly along time: up-sample by `up`, zero-phase FIR low-pass, down-sample by `down`; the
+    output has ceil(ns up / down) samples per row.  Parameters and defaults are SciPy's except `axis`: the time axis is
+    the last one here (SciPy's default is 0), and no other axis of a 2-D block is resampled (ValueError).
+
+    window: a window specification for firwin(20 max(up, down) + 1, 1 / max(up, down)) or the taps themselves (at most
+    2048, ValueError beyond).  padtype: 'constant' (the record continues as cval, 0 by default) or 'mean' (the row's float64
+    mean is removed before the filter and added back after it); SciPy's other padtypes raise ValueError.
+
+    prev_tail / next_head ([nx, n], n >= 0; padtype='constant' only): the samples before and after every row when the
+    record continues in neighbouring files.  What is given is used, beyond it the record ends; with resample_reach()
+    samples on either side the result equals the matching columns of the whole record's bit for bit.  They need
+    ns up to be a multiple of down after the reduction (otherwise consecutive files' output grids do not line up).
+
+    NumPy in -> NumPy out of the same float dtype (float64 is computed in float32); a CUDA tensor in -> a float32 CUDA
+    tensor out on the current stream without a host synchronisation; 1-D in -> 1-D out."""
+    x2, was1d = _rows_2d(trace)
+    if axis not in ((-1, 0) if was1d else (-1, 1)):
+        raise ValueError("axis = %r: only the time axis (the last one) is resampled" % (axis,))
+    if padtype not in _RESAMPLE_PADTYPES:
+        raise ValueError("padtype = %r: supported are 'constant' and 'mean'" % (padtype,))
+    if cval is not None and padtype != "constant":
+        raise ValueError('cval has no effect unless padtype is "constant"')
+    if (prev_tail is not None or next_head is not None) and padtype != "constant":
+        raise ValueError("prev_tail / next_head need padtype='constant'")
+    up, down, h = _resample_taps(up, down, window)
+    x, ld = _rows_with_pitch(x2)
+    nx, ns = x.shape
+    if ns < 1 or nx < 1:
+        raise ValueError("trace is empty")
+    taps = _taps_on_device(up, down, h, x.device)
+    left, ld_l, n_l = _neighbour(prev_tail, nx, was1d, x.device, "prev_tail")
+    right, ld_r, n_r = _neighbour(next_head, nx, was1d, x.device, "next_head")
+    y = torch.empty((nx, -(-ns * up // down)), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        off = None
+        if padtype == "mean":
+            if ld != ns:
+                x, ld = x.contiguous(), ns
+            off = torch.empty(nx, dtype=torch.float64, device=x.device)
+            mx = torch.empty(nx, dtype=torch.float32, device=x.device)
+            check(lib.d4w_row_stats_f32(dev.ptr(x), nx, ns, dev.ptr(off), dev.ptr(mx), dev.stream_ptr(x)))
+        c = 0.0 if cval is None else float(cval)
+        check(lib.d4w_resample_f32(dev.ptr(x), ld, nx, ns, None if left is None else dev.ptr(left), ld_l, n_l,
+                                   None if right is None else dev.ptr(right), ld_r, n_r, dev.ptr(taps), int(h.size), up, down,
+                                   None if off is None else dev.ptr(off), c, 1.0, 1 if padtype == "mean" else 2 if c != 0.0 else 0, dev.ptr(y),
+                                   dev.stream_ptr(x)))
+    return dev.like_input(y[0] if was1d else y, trace)
+
+
+def decimate(trace, q, n=None, ftype='fir', axis=-1, zero_phase=True):
+    """scipy.signal.decimate(trace, q, n, ftype='fir', zero_phase=True) along time: a Hamming-windowed FIR low-pass of
+    n + 1 taps (n = 20 q by default) at 1 / q of Nyquist, every q-th sample kept, ceil(ns / q) per row.  Differences from
+    SciPy: ftype defaults to 'fir' (SciPy's default is 'iir', which is not built: ValueError), and only the zero-phase
+    form exists (zero_phase=False: ValueError).  Containers as resample_poly."""
+    if ftype != "fir":
+        raise ValueError("ftype = %r: only the 'fir' form of decimate is built" % (ftype,))
+    if not zero_phase:
+        raise ValueError("zero_phase=False is not built: decimate is the zero-phase FIR form only")
+    return resample_poly(trace, 1, q, axis=axis, window=_decimate_taps(q, n))
+
+
 def _stft_mag(x2d, n_fft, hop, bin_lo, bin_hi, want_max=True):
     """|librosa.stft| of every row: returns (S [nx, bins, frames] raw magnitudes, rowmax [nx]).  want_max=False (frame
     lengths with a two-factor register transform only): the kept bins alone are formed and rowmax is None."""

@@ -496,6 +496,49 @@ int d4w_welch_f32(const float* x, int nx, int ns, int chunk, int nperseg, int no
 int d4w_chunk_energy_f32(const float* x, int nx, int ns, int chunk, float* e, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Polyphase resampling and FIR decimation along time (csrc/resample.hip):
+ * scipy.signal.resample_poly(x, up, down, axis=-1, window=h) and scipy.signal.decimate(x, q, ftype='fir') of every row,
+ * for a file that does not arrive at the rate the chain works at.  up and down are reduced by their gcd; 1 / 1 is a copy.
+ * With h = the ntaps taps (float32, DEVICE; the caller has multiplied them by up), half = (ntaps - 1) / 2 and
+ * n_out = d4w_resample_out_len(ns, up, down) = ceil(ns up / down):
+ *
+ *     y[r][m] = back_r + scale * sum_i (xv[r][i] - off_r) h[m down + half - i up],     m < n_out
+ *
+ * over all i with 0 <= m down + half - i up < ntaps for which xv[r][i] exists: xv is x[r][i] for 0 <= i < ns,
+ * left[r][n_left + i] for -n_left <= i < 0 and right[r][i - ns] for ns <= i < ns + n_right.  A sample that does not
+ * exist contributes nothing: the zero padding follows the removal of the offset.  With off = 0, scale = 1 and no
+ * neighbours this is resample_poly(padtype='constant') term for term.  Every output is summed by one thread in ascending
+ * tap order: the result is the same bits run to run and wherever a row is cut into blocks with neighbours.
+ *
+ * d4w_resample_f32: x is [nx] rows of ns float32, ld_x apart; left / right (may be NULL) hold the n_left samples before and
+ *   the n_right samples after every row, rows ld_left / ld_right apart, read in place; they need ns up % down == 0 after
+ *   the reduction (the output grids of consecutive blocks line up).  off_r = off[r] (DEVICE float64, e.g. the means of
+ *   d4w_row_stats_f32) or off_const when off == NULL; it leaves a sample as (x - hi) - lo, hi + lo its two-float form.
+ *   add_back = 0: back_r = 0;  1: back_r = off_r (padtype='mean': the offset is put back as it was);  2: back_r =
+ *   scale off_r sum_j h[t + j up] over the taps t of the output's phase -- the record continues as the constant off_r
+ *   beyond its ends (SciPy's padtype='constant' with cval; the taps of a phase sum to 1 only within ~1e-3 for up > 1).
+ *   y: float32 [nx][n_out].
+ * d4w_resample_raw_f32: the same kernel reading the raw rows c0 + r cstep, r < nx_out, of a [nch][ns] matrix
+ *   (raw_dtype as d4w_raw2strain_f32) -- the fused ingest: off_r = mean[r] (d4w_raw_row_mean_f64) is removed in float64
+ *   before the sample is rounded to float32, scale = the file's scale factor, nothing is added back, no neighbours.
+ * d4w_raw_row_mean_f64: mean[r] of those raw rows as float64; integer rows are summed as integers (exact).
+ * d4w_resample_reach: the neighbour samples the taps reach before sample 0 and after sample ns - 1 of a block whose
+ *   ns up is a multiple of down.
+ * Limits (D4W_EINVAL beyond them; there is no other path): 1 <= ntaps <= d4w_resample_max_taps() = 2048 (designed
+ * taps up to max(up, down) = 102), up and down <= 256 after the reduction.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_resample_max_taps(void);
+int d4w_resample_out_len(int ns, int up, int down);
+int d4w_resample_reach(int ntaps, int up, int down, int* n_left, int* n_right);
+int d4w_resample_f32(const float* x, size_t ld_x, int nx, int ns, const float* left, size_t ld_left, int n_left,
+                     const float* right, size_t ld_right, int n_right, const float* taps, int ntaps, int up, int down,
+                     const double* off, double off_const, double scale, int add_back, float* y, void* stream);
+int d4w_resample_raw_f32(const void* raw, int raw_dtype, int ns, int c0, int cstep, int nx_out, const float* taps,
+                         int ntaps, int up, int down, const double* mean, double scale, float* y, void* stream);
+int d4w_raw_row_mean_f64(const void* raw, int raw_dtype, int ns, int c0, int cstep, int nx_out, double* mean,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Spectrograms and spectrogram correlation: replaces dsp.get_spectrogram (dsp.py:41-78),
  * detect.get_sliced_nspectrogram (detect.py:334-408), detect.xcorr2d (detect.py:579-602),
  * detect.xcorr (detect.py:605-647) and the per-channel loop of
