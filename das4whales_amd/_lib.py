@@ -197,6 +197,13 @@ def _load():
         "d4w_assoc_select_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_int,
                                          c_void_p, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "d4w_stack_delays_i32": (c_int, [c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_int, c_void_p, c_int,
+                                         ctypes.c_double, c_void_p, c_void_p]),
+        "d4w_stack_grid_f32": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                       c_int, c_void_p, c_void_p, c_void_p]),
+        "d4w_stack_best_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+        "d4w_stack_arrivals_f64": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, ctypes.c_double, c_void_p, ctypes.c_double, c_void_p,
+                                           c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch: fail loudly

@@ -3,7 +3,8 @@
 The nine reference functions keep their names, parameter names and defaults.  The Gauss-Newton solver, the travel times and
 the misfit grid run in csrc/loc.hip (float64); `solve_lq_batch`, `misfit_grid` and `first_guess_grid` are the batched forms
 the reference does not have; `vote_grid` and `associate_picks` (csrc/assoc.hip) turn the picks of detect.pick_times* into
-the [ncalls x channel] arrival times these take.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
+the [ncalls x channel] arrival times these take; `delay_table`, `stack_grid`, `stack_best`, `arrivals_near` and
+`locate_stack` (csrc/stack.hip) get them from the envelopes themselves by a delay-and-sum over the same grid.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
 same device and stream.  The four small per-channel helpers (distances, radii, angles) are host float64 arithmetic for NumPy input, like the
 index arithmetic of the other namespaces; for tensors they stay on the device.
 
@@ -485,3 +486,254 @@ def associate_picks(picks, fs, cable_pos, c0, xs, ys, z, dt, min_picks, max_call
     if return_votes:
         info["votes"] = votes
     return _out(Ti[:ncalls], as_tensor), {k: _out(v, as_tensor) for k, v in info.items()}
+
+
+# ------------------------------------------------------------------------------------------
+# beyond the reference: delay-and-sum stack of envelopes on the position grid (csrc/stack.hip)
+# ------------------------------------------------------------------------------------------
+def _pos_finite(**kw):
+    for name, v in kw.items():
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError("%s must be positive and finite, got %r" % (name, v))
+
+
+def _grid_axes(xs, ys, device):
+    gx, gy = _f64(xs, device).reshape(-1), _f64(ys, device).reshape(-1)
+    if gx.numel() < 1 or gy.numel() < 1:
+        raise ValueError("the grid needs at least one node")
+    return gx, gy
+
+
+def _env_block(env, device):
+    """(float32 CUDA tensor [nch x ns] with unit column stride, row pitch in elements).  A column-sliced float32 CUDA view is
+    taken as it is; everything else becomes a contiguous float32 copy on the device."""
+    if getattr(env, "ndim", 0) != 2:
+        raise ValueError("env must be a 2-D [channel x time] array")
+    if env.shape[0] < 1 or env.shape[1] < 1:
+        raise ValueError("env must not be empty, got %s" % (tuple(env.shape),))
+    if (dev.is_tensor(env) and env.is_cuda and env.dtype == torch.float32 and (device is None or env.device == torch.device(device))
+            and env.stride(1) == 1 and (env.stride(0) >= env.shape[1] or env.shape[0] == 1)):
+        return env, (env.stride(0) if env.shape[0] > 1 else env.shape[1])
+    e = dev.to_device_f32(env, device)
+    return e, e.shape[1]
+
+
+def _weights(weights, nch, device):
+    if weights is None:
+        return None
+    w = dev.to_device_f32(weights if dev.is_tensor(weights) else np.asarray(weights).reshape(1, -1), device).reshape(-1)
+    if w.numel() != nch:
+        raise ValueError("weights must hold one value per channel (%d), got %d" % (nch, w.numel()))
+    return w
+
+
+def _delays(cable, c0, fs, gx, gy, z):
+    d = torch.empty((gy.numel(), gx.numel(), cable.shape[0]), dtype=torch.int32, device=cable.device)
+    _lib.check(_lib.lib.d4w_stack_delays_i32(dev.ptr(cable), cable.shape[0], c0, fs, dev.ptr(gx), gx.numel(), dev.ptr(gy), gy.numel(), z,
+                                             dev.out_ptr(d), dev.stream_ptr(cable)))
+    return d
+
+
+def delay_table(cable_pos, c0, fs, xs, ys, z):
+    """Travel times in samples from every node (xs[ix], ys[iy], z) to every channel, int32 [ny x nx x channel]:
+    d = floor(|cable_pos[ch] - node| (1 / c0) fs + 0.5) in float64.  The table stack_grid sums along; it depends on the
+    geometry and the rate only, so keep it for the consecutive files of one cable (stack_grid(..., delays=table))."""
+    cable = _cable(cable_pos, _device_of(cable_pos, xs, ys))
+    gx, gy = _grid_axes(xs, ys, cable.device)
+    c0, fs, z = float(c0), float(fs), float(z)
+    _pos_finite(c0=c0, fs=fs)
+    with torch.cuda.device(cable.device):
+        d = _delays(cable, c0, fs, gx, gy, z)
+    return _out(d, any(dev.is_tensor(a) for a in (cable_pos, xs, ys)))
+
+
+def _stack(e, pitch, table, w, nx, ny, k0, k1, normalize, form=0):
+    """The kernel on device tensors: (stack [ny x nx x (k1 - k0)], info int32 [2] = form that ran, largest tile spread)."""
+    nch, ns = e.shape
+    out = torch.empty((ny, nx, k1 - k0), dtype=torch.float32, device=e.device)
+    info = torch.empty(2, dtype=torch.int32, device=e.device)
+    _lib.check(_lib.lib.d4w_stack_grid_f32(dev.ptr(e), pitch, nch, ns, dev.ptr(table), dev.ptr(w) if w is not None else None, nx, ny,
+                                           k0, k1, int(bool(normalize)), form, dev.out_ptr(out), dev.out_ptr(info), dev.stream_ptr(e)))
+    return out, info
+
+
+def _k_range(k_range, ns):
+    k0, k1 = (0, ns) if k_range is None else (int(k_range[0]), int(k_range[1]))
+    if not k0 < k1:
+        raise ValueError("k_range = (k0, k1) must have k0 < k1, got (%d, %d)" % (k0, k1))
+    return k0, k1
+
+
+def stack_grid(env, fs, cable_pos, c0, xs, ys, z, weights=None, k_range=None, normalize=False, *, delays=None):
+    """Delay-and-sum (back-projection) of envelopes over the nodes (xs[ix], ys[iy], z):
+        stack[iy, ix, k - k0] = sum over ch of weights[ch] env[ch, k + d[iy, ix, ch]],   d = delay_table(...)
+    over the channels with weights[ch] != 0 whose sample k + d lies within the record.  A call emitted at sample k from near a
+    node adds up coherently there although it stays under a per-channel pick threshold on every channel.  Returns
+    (stack [ny x nx x nt] float32, times [nt] float64 = arange(k0, k1) / fs).
+
+    env: [channel x time] float32, e.g. dsp.envelope of a correlogram; a CUDA float32 view with unit column stride is read in
+    place (row pitch).  The stack is taken at env's rate: bring env to the rate wanted with dsp.decimate / dsp.resample_poly
+    first.  k_range = (k0, k1): emission samples, half open; default (0, ns); k0 may be negative and k1 may exceed ns.
+    weights: float32 [channel], None = ones.  A channel of weight 0 is not read at all (dead channels, the NaN rows of
+    zero_rows="nan"); a NaN under a non-zero weight propagates into every element it reaches.  normalize: divide every
+    element by the sum of the weights of the channels that contributed to it; an element without contributors is 0.
+    delays: the table of delay_table for this cable, grid, c0 and fs (built here when None).
+    float32 sums in increasing channel order, one thread per element: run-to-run bit-identical.  NumPy in -> NumPy out; a
+    CUDA tensor in -> tensors on that device and stream."""
+    device = _device_of(env, cable_pos, xs, ys, weights, delays)
+    cable = _cable(cable_pos, device)
+    gx, gy = _grid_axes(xs, ys, cable.device)
+    c0, fs, z = float(c0), float(fs), float(z)
+    _pos_finite(c0=c0, fs=fs)
+    e, pitch = _env_block(env, cable.device)
+    nch, ns = e.shape
+    if nch != cable.shape[0]:
+        raise ValueError("env has %d rows, cable_pos %d channels" % (nch, cable.shape[0]))
+    k0, k1 = _k_range(k_range, ns)
+    w = _weights(weights, nch, cable.device)
+    as_tensor = any(dev.is_tensor(a) for a in (env, cable_pos, xs, ys, weights, delays))
+    with torch.cuda.device(cable.device):
+        if delays is None:
+            table = _delays(cable, c0, fs, gx, gy, z)
+        else:
+            table = (delays if dev.is_tensor(delays) else torch.from_numpy(np.ascontiguousarray(delays))).to(cable.device, torch.int32).contiguous()
+            if tuple(table.shape) != (gy.numel(), gx.numel(), nch):
+                raise ValueError("delays must be [ny x nx x channel] = %s, got %s" % ((gy.numel(), gx.numel(), nch), tuple(table.shape)))
+        out, _ = _stack(e, pitch, table, w, gx.numel(), gy.numel(), k0, k1, normalize)
+    times = np.arange(k0, k1) / fs
+    return _out(out, as_tensor), (torch.from_numpy(times).to(cable.device) if as_tensor else times)
+
+
+def _best(s):
+    nt = s.shape[-1]
+    peak = torch.empty(nt, dtype=torch.float32, device=s.device)
+    node = torch.empty(nt, dtype=torch.int32, device=s.device)
+    _lib.check(_lib.lib.d4w_stack_best_f32(dev.ptr(s), s.numel() // nt, nt, dev.out_ptr(peak), dev.out_ptr(node), dev.stream_ptr(s)))
+    return peak, node
+
+
+def stack_best(stack):
+    """Per column of a stack [ny x nx x nt] (or [nodes x nt]): (peak [nt] float32, node [nt] int32), the largest value over the
+    nodes and its flat index iy nx + ix.  Ties go to the smallest index; a NaN never wins; a column of NaNs gives (NaN, -1)."""
+    if getattr(stack, "ndim", 0) not in (2, 3) or min(stack.shape) < 1:
+        raise ValueError("stack must be a non-empty [ny x nx x nt] or [nodes x nt] array")
+    s = dev.to_device_f32(stack, _device_of(stack))
+    with torch.cuda.device(s.device):
+        peak, node = _best(s)
+    as_tensor = dev.is_tensor(stack)
+    return _out(peak, as_tensor), _out(node, as_tensor)
+
+
+def _arrivals(e, pitch, fs, cable, c0, p, t, h, threshold, w):
+    ncalls, nch = p.shape[0], cable.shape[0]
+    Ti = torch.empty((ncalls, nch), dtype=torch.float64, device=cable.device)
+    per_channel = dev.is_tensor(threshold) or np.ndim(threshold) > 0
+    thr = None
+    if per_channel:
+        thr = _f64(threshold, cable.device).reshape(-1)
+        if thr.numel() != nch:
+            raise ValueError("threshold must be a scalar or one value per channel (%d), got %d" % (nch, thr.numel()))
+    _lib.check(_lib.lib.d4w_stack_arrivals_f64(dev.ptr(e), pitch, nch, e.shape[1], fs, dev.ptr(cable), c0, dev.ptr(p), dev.ptr(t), ncalls, h,
+                                               0.0 if per_channel else float(threshold), dev.ptr(thr) if per_channel else None,
+                                               dev.ptr(w) if w is not None else None, dev.out_ptr(Ti), dev.stream_ptr(cable)))
+    return Ti
+
+
+def arrivals_near(env, fs, cable_pos, c0, pos, t0, halfwidth, threshold, weights=None):
+    """Per-channel arrival times of calls whose position and emission time are roughly known (a node and a column of
+    stack_grid): for call c at pos[c] = (x, y, z) emitted at t0[c], the sample of the largest env[ch] within `halfwidth`
+    samples of round(t0 fs) + the travel time in samples (delay_table's function); the earliest of equal maxima, NaNs skipped.
+    Returns Ti [ncalls x channel] float64 = sample / fs, NaN where the window misses the record, weights[ch] = 0, or the
+    maximum is below `threshold` (a scalar or one value per channel): the form associate_picks returns and solve_lq_batch
+    takes.  pos: [ncalls x 3] (or [3] with a scalar t0: one call, Ti still [1 x channel])."""
+    device = _device_of(env, cable_pos, pos, t0, weights)
+    cable = _cable(cable_pos, device)
+    c0, fs = float(c0), float(fs)
+    _pos_finite(c0=c0, fs=fs)
+    h = int(halfwidth)
+    if h < 0 or h != halfwidth:
+        raise ValueError("halfwidth must be a non-negative number of samples")
+    e, pitch = _env_block(env, cable.device)
+    nch = cable.shape[0]
+    if e.shape[0] != nch:
+        raise ValueError("env has %d rows, cable_pos %d channels" % (e.shape[0], nch))
+    p = _f64(pos, cable.device)
+    p = p.reshape(1, -1) if p.dim() == 1 else p
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError("pos must be [x, y, z] or [ncalls x 3], got %s" % (tuple(p.shape),))
+    t = _f64(t0, cable.device).reshape(-1)
+    if t.numel() == 1 and p.shape[0] != 1:
+        t = t.expand(p.shape[0]).contiguous()
+    if t.numel() != p.shape[0]:
+        raise ValueError("t0 must be a scalar or one value per call")
+    w = _weights(weights, nch, cable.device)
+    as_tensor = any(dev.is_tensor(a) for a in (env, cable_pos, pos, t0, weights))
+    with torch.cuda.device(cable.device):
+        if p.shape[0] == 0:
+            Ti = torch.empty((0, nch), dtype=torch.float64, device=cable.device)
+        else:
+            Ti = _arrivals(e, pitch, fs, cable, c0, p, t, h, threshold, w)
+    return _out(Ti, as_tensor)
+
+
+def locate_stack(env, fs, cable_pos, c0, xs, ys, z, threshold, halfwidth, pick_threshold, max_calls=64, weights=None, k_range=None,
+                 normalize=False, return_stack=False):
+    """Calls from the delay-and-sum stack, without a per-channel decision before the sum: stack_grid, stack_best, the
+    package's peak picker on the one-row trace of best values (detect.pick_times(peak[None, :], threshold): prominence), the
+    `max_calls` largest of its peaks in time order, and arrivals_near at their nodes and times with `pick_threshold`.
+    Returns (Ti [ncalls x channel] float64, NaN = no arrival; info) with info a dict of
+      first_guess [ncalls x 4]  the node's x, y, z and times[column]: what solve_lq_batch(first_guess=...) takes
+      node, column [ncalls] int32, value [ncalls] float32: flat node index iy nx + ix, column of the stack, the peak there
+      npicks [ncalls] int32     non-NaN entries of each row of Ti
+      times [nt]                emission time of every column
+      stack, peak, best_node    with return_stack: the results of stack_grid and stack_best
+    Without a call Ti is [0 x channel].  The stack, the best node, the picker and the arrivals are the library's kernels; around
+    them the call reads the trace of best values, its nodes and the picker's columns back to the host (three small copies, the
+    only synchronisations) to choose the `max_calls` peaks there, uploads their nodes and times, and counts `npicks` with a few
+    small torch operations on the [ncalls x channel] result.  See stack_grid for env (bring it to the rate wanted with dsp.decimate /
+    dsp.resample_poly first), weights, k_range and normalize, arrivals_near for halfwidth and pick_threshold."""
+    from . import detect
+    max_calls = int(max_calls)
+    if max_calls < 0:
+        raise ValueError("max_calls must not be negative")
+    if int(halfwidth) < 0:
+        raise ValueError("halfwidth must be a non-negative number of samples")
+    device = _device_of(env, cable_pos, xs, ys, weights)
+    cable = _cable(cable_pos, device)
+    gx, gy = _grid_axes(xs, ys, cable.device)
+    c0, fs, z = float(c0), float(fs), float(z)
+    _pos_finite(c0=c0, fs=fs)
+    e, pitch = _env_block(env, cable.device)
+    nch, ns = e.shape
+    if nch != cable.shape[0]:
+        raise ValueError("env has %d rows, cable_pos %d channels" % (nch, cable.shape[0]))
+    k0, k1 = _k_range(k_range, ns)
+    w = _weights(weights, nch, cable.device)
+    as_tensor = any(dev.is_tensor(a) for a in (env, cable_pos, xs, ys, weights))
+    d, nx = cable.device, gx.numel()
+    times = np.arange(k0, k1) / fs
+    with torch.cuda.device(d):
+        table = _delays(cable, c0, fs, gx, gy, z)
+        stack, _ = _stack(e, pitch, table, w, nx, gy.numel(), k0, k1, normalize)
+        peak, best_node = _best(stack)
+        cols = detect.pick_times(peak[None, :], threshold).packed[1].cpu().numpy()
+        peak_h, node_h = peak.cpu().numpy(), best_node.cpu().numpy()
+        cols = cols[node_h[cols] >= 0]
+        if len(cols) > max_calls:                                # the largest peaks, the earlier of equals
+            cols = cols[np.lexsort((cols, -peak_h[cols].astype(np.float64)))[:max_calls]]
+        cols = np.sort(cols)
+        nodes = node_h[cols].astype(np.int64)
+        fg = np.empty((len(cols), 4))
+        fg[:, 0], fg[:, 1] = gx.cpu().numpy()[nodes % nx], gy.cpu().numpy()[nodes // nx]
+        fg[:, 2], fg[:, 3] = z, times[cols]
+        fg_d = torch.from_numpy(fg).to(d)
+        if len(cols):
+            Ti = _arrivals(e, pitch, fs, cable, c0, fg_d[:, :3].contiguous(), fg_d[:, 3].contiguous(), int(halfwidth), pick_threshold, w)
+        else:
+            Ti = torch.empty((0, nch), dtype=torch.float64, device=d)
+        info = {"first_guess": fg_d, "node": torch.from_numpy(nodes.astype(np.int32)).to(d),
+                "column": torch.from_numpy(cols.astype(np.int32)).to(d), "value": torch.from_numpy(peak_h[cols]).to(d),
+                "npicks": (~torch.isnan(Ti)).sum(1).to(torch.int32), "times": torch.from_numpy(times).to(d)}
+        if return_stack:
+            info.update(stack=stack, peak=peak, best_node=best_node)
+    return _out(Ti, as_tensor), {k: _out(v, as_tensor) for k, v in info.items()}

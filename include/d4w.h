@@ -773,6 +773,54 @@ int d4w_assoc_select_f64(const int64_t* picks, int npicks, const int64_t* offset
                          int call, const int32_t* state, int32_t* rec, int32_t* assigned, double* Ti, int32_t* chosen,
                          double* e_chosen, double* first_guess, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Delay-and-sum stack of envelopes over the position grid (das4whales_amd/csrc/stack.hip): the soft-decision twin of the
+ * vote above -- no per-channel threshold comes before the sum over the channels (the reference has none of this).  Every
+ * pointer is DEVICE memory.  Layouts as above: cable_pos [nch][3] float64, node g = iy nx + ix at (xs[ix], ys[iy], z).
+ *
+ *   env [nch][ns] float32 with a row pitch in ELEMENTS (pitch >= ns: a column-sliced view is read in place), the envelope of
+ *     a correlogram; weights [nch] float32, or NULL for ones.
+ *   d[g][ch] = (int) floor(|cable_pos[ch] - node_g| * (1 / c0) * fs + 0.5)        travel time in samples, float64, capped
+ *     at 2^30; the same difference / square-root expression as the vote, 1 / c0 formed once on the host, no contraction.
+ *   stack[g][k - k0] = sum over ch, in increasing ch, of weights[ch] * env[ch][k + d[g][ch]]             k0 <= k < k1
+ *     over the channels with weights[ch] != 0 and 0 <= k + d[g][ch] < ns
+ *
+ * d4w_stack_delays_i32: delays [ny nx][nch] int32 = d.  One thread per element.
+ * d4w_stack_grid_f32: stack [ny nx][k1 - k0] float32 from env and a delay table (d4w_stack_delays_i32's; kept by the caller
+ *   across the files of one geometry).  Columns are emission samples k0 .. k1 - 1; k0 may be negative and k1 may exceed ns
+ *   (-2^30 <= k0 < k1 <= 2^30, k1 - k0 <= 2^31 - 1).  float32 accumulation, one fmaf per term, in increasing channel order, every element by one
+ *   thread: no atomics, no split over the channels, run-to-run bit-identical.  A channel of weight 0 is not read at all
+ *   (dead channels, NaN rows); a NaN under a non-zero weight propagates.  normalize != 0: every element is divided by the
+ *   sum of the weights of the channels that contributed to it, accumulated beside it in the same order; an element without
+ *   contributors (or whose contributing weights sum to 0) is 0.
+ *   form: 1 = window (a workgroup owns 4 x 4 neighbouring nodes and 1024 columns, and stages per channel the contiguous span
+ *   of env the tile needs in LDS, double-buffered), 2 = direct (the same loop reading env from global memory), 0 = window
+ *   if the table's largest delay spread within a tile (max over tiles and channels of max d - min d over the tile's nodes)
+ *   is at most 992 samples, else direct.  The choice is made on the device; both forms give the same bits.
+ *   info = int32 [2], written by the call: info[0] = the form that ran (1 or 2; -1 when form = 1 was asked of a table whose
+ *   spread exceeds the window, and stack is then left untouched), info[1] = that largest spread (0 with form = 2, which does
+ *   not look).  info may be NULL with form = 2 only.
+ * d4w_stack_best_f32: per column the largest value over the ngrid nodes and its node: peak [nt] float32, node [nt] int32.
+ *   Ties go to the smallest g; a NaN never wins; a column of NaNs gives (NaN, -1).  stack = [ngrid][nt].
+ * d4w_stack_arrivals_f64: Ti [ncalls][nch] float64, the form d4w_loc_solve_f64 takes.  For call c at pos[c] = (x, y, z)
+ *   (pos [ncalls][3]) emitted at t0[c]: kc = floor(t0[c] fs + 0.5), m = kc + d(pos[c], ch) with the delay function above;
+ *   over the samples i in [m - halfwidth, m + halfwidth] and [0, ns) the largest env[ch][i], the earliest of equals, NaNs
+ *   skipped.  Ti[c][ch] = i / fs (a true division), or NaN when the window is empty, weights[ch] = 0, t0[c] is not finite, or
+ *   the maximum is below the threshold: thresholds[ch] (float64 [nch]) if given, else the scalar `threshold`.
+ *   One wave per (call, channel).
+ * Errors: D4W_EINVAL for a NULL required pointer, nch, ns, nx, ny or ncalls < 1, pitch < ns, fs or c0 not finite or <= 0,
+ *   k0 >= k1, k0 < -2^30, k1 > 2^30 or k1 - k0 > 2^31 - 1, halfwidth < 0, a form outside 0 .. 2, info = NULL with form 0 or 1,
+ *   more than 65535 tiles of 4 x 4 nodes.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_stack_delays_i32(const double* cable_pos, int nch, double c0, double fs, const double* xs, int nx, const double* ys, int ny,
+                         double z, int32_t* delays, void* stream);
+int d4w_stack_grid_f32(const float* env, int64_t pitch, int nch, int ns, const int32_t* delays, const float* weights, int nx, int ny,
+                       int k0, int k1, int normalize, int form, float* stack, int32_t* info, void* stream);
+int d4w_stack_best_f32(const float* stack, int ngrid, int nt, float* peak, int32_t* node, void* stream);
+int d4w_stack_arrivals_f64(const float* env, int64_t pitch, int nch, int ns, double fs, const double* cable_pos, double c0,
+                           const double* pos, const double* t0, int ncalls, int halfwidth, double threshold,
+                           const double* thresholds, const float* weights, double* Ti, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
