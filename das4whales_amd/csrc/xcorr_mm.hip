@@ -27,7 +27,7 @@
 // FFT kernel's (tests/test_rowops_gpu.py).
 //
 // Launch shape.  Persistent workgroups (256 threads, 4 waves) walk a row in CHUNKS of CH lags: 4096 (kMmCH) for one template,
-// 8192 (kMmCHPair) where two templates share the launch.  A chunk is G = CH / 4096 GROUPS of 4096 lags (kMmGroup), each
+// 8192 (kMmCHPair) or 4096 (kMmCHPairTail) where two templates share the launch.  A chunk is G = CH / 4096 GROUPS of 4096 lags (kMmGroup), each
 // staged with its own halo of 32 KS samples, its own scale and its own prefix carry (MmGeom), so a lag's arithmetic does not
 // depend on CH.  The chunk's CH + halo samples are loaded one chunk AHEAD into registers, converted and written to one of
 // two LDS buffers (hi / lo arrays in sample order: the four lane groups of a fragment read hit 16 different 16-byte slots
@@ -41,7 +41,8 @@
 namespace d4w {
 
 constexpr int kMmCH = 4096;                      // lags per chunk of the one-template kernels
-constexpr int kMmCHPair = 8192;                  // ... of the two-template kernels (0.22 ms faster there, 2.4 ms slower for one template: DESIGN 3.3)
+constexpr int kMmCHPair = 8192;                  // ... of the two-template kernels whose chunks are dealt over the grid (5.65 against 5.74 ms at 4096) ...
+constexpr int kMmCHPairTail = 4096;              // ... and of those that walk whole rows, the TAIL kernels (5.89 against 5.95 ms at 8192): profiles/mm_lean/README.md
 constexpr int kMmGroup = 4096;                   // a longer chunk is staged, scaled and prefix-summed in GROUPS of this many lags: the arithmetic of a lag
                                                  // does not depend on the chunk length its kernel walks the row in
 constexpr int kMmKS = 6;                         // k-steps of 32 of the two-template kernels -> Toeplitz depth 192, supports <= 177
@@ -100,6 +101,14 @@ struct MmArgs {
 // in the tile's epilogue, hipcc schedules the TAIL kernels differently.)
 __device__ __forceinline__ int mm_tile(int wv, int ti) { return wv + 4 * ti; }
 
+// issue priority of this wave among the waves of its SIMD (s_setprio: 0 is the default, higher is served first)
+template <int V>
+__device__ __forceinline__ void mm_wave_priority() {
+#ifndef D4W_EMU
+    __builtin_amdgcn_s_setprio(V);
+#endif
+}
+
 // inclusive prefix sum over the 64 lanes of a wave: four row_shr steps inside the 16-lane DPP rows, then row_bcast:15 /
 // row_bcast:31 carry the row totals on (six v_add_f32 with DPP operands, no LDS traffic)
 __device__ __forceinline__ float mm_wave_scan(float v) {
@@ -151,9 +160,6 @@ __device__ __forceinline__ float mm_wave_scan(float v) {
 // (A form with the WAVES split between two templates at three workgroups per CU was built in round 6 and measured slower,
 // 6.32 against 6.11 ms: DESIGN.md 3.3, profiles/r06m.)
 //
-// Probe builds (scripts/probe/mm_variants.sh), timing only -- each returns WRONG values: D4W_MM_V_NOCONV awaits the loads and
-// converts nothing, D4W_MM_V_NOMFMA leaves out the matrix products, D4W_MM_V_NOSTORE writes nothing.  They stay until the
-// phase table they exist for (profiles/mm_pair/README.md, step 4) has been measured on hardware.
 template <int KS0, int KS1, int WPS, bool TAIL = false, bool WMAX = false, int CH = kMmCH>
 __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
     constexpr int KSM = KS0 > KS1 ? KS0 : KS1;
@@ -260,8 +266,16 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
     bool heavy_n = false;                                           // the row is (nearly) all offset: scale it group by group
     bool tail_n = false;                                            // the chunk reaches beyond the row (wave-uniform)
     int c0_n = 0;
+    // LEAN chunks (two-template kernels): the whole stage lies inside a row that needs none of the special cases -- 16-byte
+    // aligned rows of a multiple of four samples, scaled by the caller's 1 / max|x| (not heavy), no clamp, no continuation, no
+    // accumulation.  Such a chunk takes a loop body compiled without those paths (below); the decision is wave-uniform, per
+    // launch (lean_launch), per row (heavy_n) and per chunk (the stage's end).  The arithmetic of a lag is the same in both.
+    constexpr bool kLean = KS1 > 0;
+    const bool lean_launch = kLean && P.maxabs && !P.clamp && !P.accumulate && ((ns | P.shift) & 3) == 0 &&
+                             ((reinterpret_cast<uintptr_t>(P.x) | reinterpret_cast<uintptr_t>(P.y0) | reinterpret_cast<uintptr_t>(P.y1)) & 15) == 0;
+    bool lean_n = false;                                            // the chunk being loaded is one
 
-    auto issue = [&]() {                                            // global loads of chunk (row_n, cin_n) into pre[]
+    auto issue = [&]() {                                          // global loads of chunk (row_n, cin_n) into pre[]
         c0_n = cin_n * CH;
         if (!kRows || cin_n == 0) {                                 // the row's statistics: once per row where a workgroup walks whole rows
             mu_n = mean2_load(P.mean, row_n);
@@ -276,6 +290,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
         }
         const int s0 = c0_n + P.shift;                              // first sample of the chunk's stage
         tail_n = s0 + kMmStage > ns;
+        lean_n = lean_launch && !heavy_n && !tail_n;
         const float* xr = P.x + roff_n;
         const bool al = (reinterpret_cast<uintptr_t>(xr + s0) & 15) == 0;
         if (al && s0 + kMmStage <= ns) {
@@ -330,20 +345,29 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
     int buf = 0;
     // TAIL: prefix of the normalised row at the chunk's first sample, a float64 kept as two wave-uniform floats (scalar registers)
     float pst_hi = 0.f, pst_lo = 0.f;
-    for (bool more = more_n; more; more = more_n) {
+    // One chunk: convert what issue() loaded, request the next chunk, one barrier, the tiles.  LEAN (see lean_n): compiled
+    // without the row-end selects and compares, the scalar load / store paths, the group's own scale with its reduction and
+    // barrier, and the clamp.  The software pipeline runs across the two forms: pre[], the buffer parity, the prefix carry and
+    // the row's statistics are the same variables, and a chunk requested by one form may be computed by the other.
+    auto chunk = [&](auto lean_c) {
+        constexpr bool LEAN = decltype(lean_c)::value;
         const int row = row_n, c0 = c0_n, cin = cin_n;             // the chunk to compute: its row, first lag, number inside the row
         const size_t roff = roff_n;
         const Mean2 mu = mu_n;
-        const bool tail = tail_n;
+        const bool tail = LEAN ? false : tail_n;
         const int n_valid = ns + ((P.xnext && P.n_next > 0) ? P.n_next : 0) - c0 - P.shift;     // samples of the stage that exist
         const float gout = g_n;                                     // the normalisation's factor, applied to the outputs when a group scales itself
-        const bool own_scale = !P.maxabs || heavy_n;                // wave- and workgroup-uniform (one row per chunk)
+        const bool own_scale = LEAN ? false : (!P.maxabs || heavy_n);   // wave- and workgroup-uniform (one row per chunk)
         float gsc[G], osx[G];                                       // per group: x scale applied before the split, and what undoes it
         static_for<G>([&](auto gg) { gsc[decltype(gg)::value] = g_n; osx[decltype(gg)::value] = 1.f; });
         mm_half* bh = lds + (size_t)buf * 2 * kMmArr;
         mm_half* bl = bh + kMmArr;
         advance();
         if (TAIL && cin == 0) { pst_hi = 0.f; pst_lo = 0.f; }
+        // (lean chunks: a wave that converts is served before the waves of the other workgroup that are in their matrix phase --
+        // it reaches the barrier and requests the next chunk sooner, and its vector work fills the gaps between their products;
+        // 0.07-0.1 ms of 6.1, profiles/mm_lean/README.md)
+        if constexpr (LEAN) mm_wave_priority<1>();
         // load q of a lane lies in group q / QG (the chunk's own halo, the last load, in the last group); the first load of a
         // later group holds, in its first kMmHalo / 4 lanes, the halo of the group before as well
         // ---- convert the loaded chunk: (x - mu) * scale -> hi / lo halves in LDS
@@ -397,7 +421,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             // the next file's head (or statistics that are not the rows' own, D4W_MM_CLAMP=1) may leave |v| beyond binary16's
             // range: inf - inf would turn a whole tile into NaN where the float32 forms stay finite; one v_med3_f32 per
             // sample, only where asked for (a kernel argument: a scalar branch)
-            if (P.clamp && !own_scale) static_for<4>([&](auto ee) { constexpr int e = decltype(ee)::value; s[e] = mm_clamp_half(s[e]); });
+            if (!LEAN && P.clamp && !own_scale) static_for<4>([&](auto ee) { constexpr int e = decltype(ee)::value; s[e] = mm_clamp_half(s[e]); });
             if (tail) {                                              // beyond the data: the zero padding of the correlation
                 static_for<4>([&](auto ee) { constexpr int e = decltype(ee)::value; if (at + e >= n_valid) s[e] = 0.f; });
             }
@@ -407,11 +431,7 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             float s[4] = {0.f, 0.f, 0.f, 0.f};
             const bool mine = q < kMmQ - 1 || tid < kMmLastQ;
             const int at = 4 * (tid + q * kMmThreads);              // the lane's first sample inside the chunk
-#ifdef D4W_MM_V_NOCONV              // (probe build, see above the kernel)
-            if (mine && pre[q].x == 1.2345e30f) {
-#else
             if (mine) {
-#endif
                 scaled(pre[q], at, std::integral_constant<int, gq>{}, s);
                 // group gq's stage starts at gq (GL + halo) in the arrays: sample `at` of the chunk sits gq halos further on
                 mm_split_put4(s, bh + (at + gq * kMmHalo), bl + (at + gq * kMmHalo));
@@ -434,11 +454,12 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
         });
         // ---- next chunk's loads fly across the barrier and the matrix phase
         if (more_n) issue();
+        if constexpr (LEAN) mm_wave_priority<0>();
         lds_barrier();
         // ---- CH / 256 tiles of 256 lags, a quarter per wave: C[i][a] (+)= A[i][u] B[u][a]
         float* ya = P.y0 + roff;
         float* yb = KS1 ? P.y1 + roff : nullptr;
-        const bool valign = ((reinterpret_cast<uintptr_t>(ya + c0) & 15) == 0) && (!KS1 || (reinterpret_cast<uintptr_t>(yb + c0) & 15) == 0);
+        const bool valign = LEAN || (((reinterpret_cast<uintptr_t>(ya + c0) & 15) == 0) && (!KS1 || (reinterpret_cast<uintptr_t>(yb + c0) & 15) == 0));
         float oxs[G], o0[G], o1[G];
         static_for<G>([&](auto gg) {
             constexpr int gi = decltype(gg)::value;
@@ -469,6 +490,91 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
         mm_f4 c0h = mm_zero(), c0l = mm_zero(), c1h = mm_zero(), c1l = mm_zero();
         float vmax0 = -INFINITY, vmax1 = -INFINITY;                 // this lane's largest stored value of the chunk
         float vsum = 0.f;                                           // ... and a sum that is NaN when any stored value was (np.max propagates NaN)
+        // a complete tile (the wave's ti-th): scale, combine, stream out
+        auto finish = [&](auto tt) {
+            constexpr int ti = decltype(tt)::value;
+            constexpr int tg = 4 * ti / TG;                     // the tile's group
+            const int T = mm_tile(wv, ti);
+            const int kl = 256 * T + 16 * n16 + 4 * g;          // this lane's four lags inside the chunk ...
+            const int k = c0 + kl;                              // ... and inside the row
+            if constexpr (ti == 0) {
+                // (here, not ahead of the matrix instructions: nothing before the first tile's end needs it)
+                // TAIL: the prefix at each segment's start (lane l: segment l of the group) and the group's sum, which moves the
+                // row's prefix on (every wave forms the same values from the same LDS words)
+                if constexpr (TAIL) {
+                    static_for<G>([&](auto gg) {
+                        constexpr int gi = decltype(gg)::value;
+                        const float w = lane < 16 ? wt[buf * 16 * G + 16 * gi + lane] : 0.f;
+                        const float inc = mm_wave_scan(w);
+                        segoff[gi] = inc - w;
+                        pstg[gi] = pst_hi;
+#ifdef D4W_EMU
+                        const float own = __shfl(inc, 15);
+#else
+                        const float own = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inc), 15));
+#endif
+                        const double pd = ((double)pst_hi + (double)pst_lo) + (double)(own * oxs[gi]);
+                        const float ph = (float)pd, pl2 = (float)(pd - (double)ph);
+#ifdef D4W_EMU
+                        pst_hi = ph; pst_lo = pl2;
+#else
+                        pst_hi = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ph)));
+                        pst_lo = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pl2)));
+#endif
+                    });
+                }
+            }
+            float r0[4], r1[4];
+            float a0 = 0.f, a1 = 0.f;                           // TAIL: tail_t x (prefix at the block's first sample), the same for the lane's four lags
+            if constexpr (TAIL) {
+                // tile T = the segment this wave converted: row prefix at the group + segment offset + block prefix
+#ifdef D4W_EMU
+                const float so = __shfl(segoff[tg], T - tg * TG);
+#else
+                const float so = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, segoff[tg]), T - tg * TG));
+#endif
+                // (tile T = segment T of the stage = load T / 4 of wave T % 4)
+                const int pi = G == 1 ? kMmThreads * (T >> 2) + 64 * (T & 3) + 4 * n16 : (kMmThreads / 4) * (T >> 2) + 16 * (T & 3) + n16;
+                const float pbk = fmaf(so + pb[buf * kPb + pi], oxs[tg], pstg[tg]);
+                a0 = P.tail0 * pbk;
+                a1 = P.tail1 * pbk;
+            }
+            static_for<4>([&](auto rr) {
+                constexpr int r = decltype(rr)::value;
+                // (the tail's addend rides the scaling multiply: an FMA instead of a multiply)
+                r0[r] = fmaf(fmaf(mm_get(c0l, r), kMmLoInv, mm_get(c0h, r)), o0[tg], a0);
+                if constexpr (KS1 > 0) r1[r] = fmaf(fmaf(mm_get(c1l, r), kMmLoInv, mm_get(c1h, r)), o1[tg], a1);
+            });
+            c0h = mm_zero(); c0l = mm_zero(); c1h = mm_zero(); c1l = mm_zero();
+            if (LEAN || (valign && k + 3 < ns)) {        // (a lean chunk's lags all lie inside the row)
+                if (KS1 == 0 && P.accumulate) {                 // a later section of a long template
+                    const float4 o = mm_load4_stream(reinterpret_cast<const float4*>(ya + k));
+                    r0[0] += o.x; r0[1] += o.y; r0[2] += o.z; r0[3] += o.w;
+                }
+                mm_store4(ya + k, r0[0], r0[1], r0[2], r0[3]);
+                if constexpr (KS1 > 0) mm_store4(yb + k, r1[0], r1[1], r1[2], r1[3]);
+                if (WMAX) {
+                    vmax0 = fmaxf(vmax0, fmaxf(fmaxf(r0[0], r0[1]), fmaxf(r0[2], r0[3])));
+                    vsum += (r0[0] + r0[1]) + (r0[2] + r0[3]);
+                    if constexpr (KS1 > 0) {
+                        vmax1 = fmaxf(vmax1, fmaxf(fmaxf(r1[0], r1[1]), fmaxf(r1[2], r1[3])));
+                        vsum += (r1[0] + r1[1]) + (r1[2] + r1[3]);
+                    }
+                }
+            } else {                                            // a row end or an unaligned row (tiles beyond the row: nothing)
+                for (int r = 0; r < 4; ++r)
+                    if (k + r < ns) {
+                        const float v0 = (KS1 == 0 && P.accumulate) ? ya[k + r] + r0[r] : r0[r];
+                        ya[k + r] = v0;
+                        if constexpr (KS1 > 0) yb[k + r] = r1[r];
+                        if (WMAX) {
+                            vmax0 = fmaxf(vmax0, v0);
+                            vsum += v0;
+                            if constexpr (KS1 > 0) { vmax1 = fmaxf(vmax1, r1[r]); vsum += r1[r]; }
+                        }
+                    }
+            }
+        };
         static_for<NST>([&](auto ss) {
             constexpr int s_ = decltype(ss)::value, ti = s_ / KSM, kk = s_ % KSM;
             if constexpr (s_ + PF < NST) {
@@ -477,7 +583,6 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             }
             mm_sched_fence();
             const mm_h8 xh = fh[s_ % (PF + 1)], xl = fl[s_ % (PF + 1)];
-#ifndef D4W_MM_V_NOMFMA             // (probe build)
             if constexpr (kk < KS0) {
                 c0h = mm_mfma(a0h[kk], xh, c0h);
                 c0l = mm_mfma(a0h[kk], xl, c0l);
@@ -488,97 +593,8 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             }
             if constexpr (kk < KS0) c0l = mm_mfma(a0l[kk], xh, c0l);
             if constexpr (kk < KS1) c1l = mm_mfma(a1l[kk], xh, c1l);
-#else
-            c0h[0] += (float)xh[0]; c0l[0] += (float)xl[0];
-#endif
             mm_sched_fence();
-            if constexpr (kk == KSM - 1) {                          // the tile is complete: scale, combine, stream out
-                constexpr int tg = 4 * ti / TG;                     // the tile's group
-                const int T = mm_tile(wv, ti);
-                const int kl = 256 * T + 16 * n16 + 4 * g;          // this lane's four lags inside the chunk ...
-                const int k = c0 + kl;                              // ... and inside the row
-                if constexpr (ti == 0) {
-                    // (here, not ahead of the matrix instructions: nothing before the first tile's end needs it)
-                    // TAIL: the prefix at each segment's start (lane l: segment l of the group) and the group's sum, which moves the
-                    // row's prefix on (every wave forms the same values from the same LDS words)
-                    if constexpr (TAIL) {
-                        static_for<G>([&](auto gg) {
-                            constexpr int gi = decltype(gg)::value;
-                            const float w = lane < 16 ? wt[buf * 16 * G + 16 * gi + lane] : 0.f;
-                            const float inc = mm_wave_scan(w);
-                            segoff[gi] = inc - w;
-                            pstg[gi] = pst_hi;
-#ifdef D4W_EMU
-                            const float own = __shfl(inc, 15);
-#else
-                            const float own = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inc), 15));
-#endif
-                            const double pd = ((double)pst_hi + (double)pst_lo) + (double)(own * oxs[gi]);
-                            const float ph = (float)pd, pl2 = (float)(pd - (double)ph);
-#ifdef D4W_EMU
-                            pst_hi = ph; pst_lo = pl2;
-#else
-                            pst_hi = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ph)));
-                            pst_lo = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pl2)));
-#endif
-                        });
-                    }
-                }
-                float r0[4], r1[4];
-                float a0 = 0.f, a1 = 0.f;                           // TAIL: tail_t x (prefix at the block's first sample), the same for the lane's four lags
-                if constexpr (TAIL) {
-                    // tile T = the segment this wave converted: row prefix at the group + segment offset + block prefix
-#ifdef D4W_EMU
-                    const float so = __shfl(segoff[tg], T - tg * TG);
-#else
-                    const float so = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, segoff[tg]), T - tg * TG));
-#endif
-                    // (tile T = segment T of the stage = load T / 4 of wave T % 4)
-                    const int pi = G == 1 ? kMmThreads * (T >> 2) + 64 * (T & 3) + 4 * n16 : (kMmThreads / 4) * (T >> 2) + 16 * (T & 3) + n16;
-                    const float pbk = fmaf(so + pb[buf * kPb + pi], oxs[tg], pstg[tg]);
-                    a0 = P.tail0 * pbk;
-                    a1 = P.tail1 * pbk;
-                }
-                static_for<4>([&](auto rr) {
-                    constexpr int r = decltype(rr)::value;
-                    // (the tail's addend rides the scaling multiply: an FMA instead of a multiply)
-                    r0[r] = fmaf(fmaf(mm_get(c0l, r), kMmLoInv, mm_get(c0h, r)), o0[tg], a0);
-                    if constexpr (KS1 > 0) r1[r] = fmaf(fmaf(mm_get(c1l, r), kMmLoInv, mm_get(c1h, r)), o1[tg], a1);
-                });
-                c0h = mm_zero(); c0l = mm_zero(); c1h = mm_zero(); c1l = mm_zero();
-#ifdef D4W_MM_V_NOSTORE             // (probe build)
-                if (r0[0] != 1.2345e30f) { }
-                else
-#endif
-                if (valign && k + 3 < ns) {
-                    if (KS1 == 0 && P.accumulate) {                 // a later section of a long template
-                        const float4 o = mm_load4_stream(reinterpret_cast<const float4*>(ya + k));
-                        r0[0] += o.x; r0[1] += o.y; r0[2] += o.z; r0[3] += o.w;
-                    }
-                    mm_store4(ya + k, r0[0], r0[1], r0[2], r0[3]);
-                    if constexpr (KS1 > 0) mm_store4(yb + k, r1[0], r1[1], r1[2], r1[3]);
-                    if (WMAX) {
-                        vmax0 = fmaxf(vmax0, fmaxf(fmaxf(r0[0], r0[1]), fmaxf(r0[2], r0[3])));
-                        vsum += (r0[0] + r0[1]) + (r0[2] + r0[3]);
-                        if constexpr (KS1 > 0) {
-                            vmax1 = fmaxf(vmax1, fmaxf(fmaxf(r1[0], r1[1]), fmaxf(r1[2], r1[3])));
-                            vsum += (r1[0] + r1[1]) + (r1[2] + r1[3]);
-                        }
-                    }
-                } else {                                            // a row end or an unaligned row (tiles beyond the row: nothing)
-                    for (int r = 0; r < 4; ++r)
-                        if (k + r < ns) {
-                            const float v0 = (KS1 == 0 && P.accumulate) ? ya[k + r] + r0[r] : r0[r];
-                            ya[k + r] = v0;
-                            if constexpr (KS1 > 0) yb[k + r] = r1[r];
-                            if (WMAX) {
-                                vmax0 = fmaxf(vmax0, v0);
-                                vsum += v0;
-                                if constexpr (KS1 > 0) { vmax1 = fmaxf(vmax1, r1[r]); vsum += r1[r]; }
-                            }
-                        }
-                }
-            }
+            if constexpr (kk == KSM - 1) finish(std::integral_constant<int, ti>{});
         });
         if (WMAX) {                                             // one atomic per wave, chunk and template
             for (int o = 32; o > 0; o >>= 1) {
@@ -595,6 +611,15 @@ __global__ __launch_bounds__(kMmThreads, WPS) void xcorr_mm_rows(MmArgs P) {
             }
         }
         buf ^= 1;
+    };
+    if constexpr (kLean) {
+        // the lean chunks of a row as a loop of their own: what only the general form needs is not kept in registers across it
+        while (more_n) {
+            while (more_n && lean_n) chunk(std::true_type{});
+            if (more_n) chunk(std::false_type{});
+        }
+    } else {
+        while (more_n) chunk(std::false_type{});
     }
 }
 
@@ -606,7 +631,7 @@ using namespace d4w;
 //   mm_wps           workgroups per CU an instantiation's registers are budgeted for
 //   mm_launch        one launch: row maxima or not, the LDS size of the instantiation's own geometry
 //   mm_one_section   one template of <= 497 taps -> the 6-, 8-, 12- or 16-step kernel
-//   mm_pair          two templates of <= 177 taps -> the <5, 6> or <6, 6> kernel on chunks of kMmCHPair lags
+//   mm_pair          two templates of <= 177 taps -> the <5, 6> or <6, 6> kernel on chunks of kMmCHPair (with the tail: kMmCHPairTail) lags
 //   mm_one_template  one template of any support: sections of equal length through mm_one_section
 // and d4w_xcorr_mm_tail_f32 below chooses the grid and between mm_pair and mm_one_template.
 
@@ -641,8 +666,9 @@ static int mm_one_section(const MmArgs& Q, int grid, void* stream) {
 
 template <bool TAIL>
 static int mm_pair(const MmArgs& P, int grid, void* stream) {
-    if (ceil_div(P.len0 + 15, 32) <= 5) return mm_launch<5, kMmKS, TAIL, kMmCHPair>(P, grid, stream);
-    return mm_launch<kMmKS, kMmKS, TAIL, kMmCHPair>(P, grid, stream);
+    constexpr int CH = TAIL ? kMmCHPairTail : kMmCHPair;
+    if (ceil_div(P.len0 + 15, 32) <= 5) return mm_launch<5, kMmKS, TAIL, CH>(P, grid, stream);
+    return mm_launch<kMmKS, kMmKS, TAIL, CH>(P, grid, stream);
 }
 
 // one template of any support <= d4w_xcorr_mm_max_support(): sections of kMmSection taps, the first one overwriting y, the
@@ -727,8 +753,8 @@ int d4w_xcorr_mm_tail_f32(const float* x, int nx, int ns, const float* xnext, in
     // for another day.  D4W_MM_WGS overrides the count (measurements).
     static const int env_wgs = [] { const char* v = getenv("D4W_MM_WGS"); const int n = v ? atoi(v) : 0; return n < 0 ? 0 : (n > 8 ? 8 : n); }();
     const int ks0 = ceil_div(len0 + 15, 32), ks1 = ceil_div(len1 + 15, 32);
-    // two templates of <= 177 samples share a launch: every wave both templates, chunks of kMmCHPair lags; every other kernel
-    // walks chunks of kMmCH
+    // two templates of <= 177 samples share a launch: every wave both templates, chunks of kMmCHPair lags where they are dealt
+    // over the grid (the count below; with a tail the grid counts rows); every other kernel walks chunks of kMmCH
     const bool fused = ntpl == 2 && std::max(ks0, ks1) <= kMmKS;
     const int nchunk = ceil_div(ns, fused ? kMmCHPair : kMmCH);
     const int per_cu = env_wgs ? env_wgs : ((ntpl == 1 && ks0 <= kMmKS) ? 3 : 2);
