@@ -491,6 +491,92 @@ def compute_cross_correlogram(data, template, exact_tail=None, zero_rows=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# window-normalised matched filter (no reference counterpart; DESIGN.md 3.3a, csrc/nmf.hip)
+# ---------------------------------------------------------------------------------------------
+def _nmf_parts(template):
+    """(h', |h'|) of a template for the window-normalised matched filter: the support as _normalised_support cuts it, de-meaned
+    over the SUPPORT (the zero-padded length and its DC tail have no place here) and scaled by 1 / max|h| (the scale cancels);
+    the norm is that of the float32 taps the correlator receives."""
+    t = _host_vec(template)
+    h = t[:_support(t)]
+    a = np.max(np.abs(h))
+    if a == 0:
+        raise ValueError("template is all zeros")
+    if len(h) > int(lib.d4w_nmf_max_support()):
+        raise ValueError("the window-normalised matched filter takes supports <= %d samples (got %d)"
+                         % (int(lib.d4w_nmf_max_support()), len(h)))
+    hp = (h - h.mean()) / a
+    return hp, float(np.sqrt(np.sum(hp.astype(np.float32).astype(np.float64) ** 2)))
+
+
+def _nmf_device(x, taps, norms, center=True, floor=1e-6, stats=None, next_head=None, want_row_max=False):
+    """Window-normalised correlograms of the rows of x (float32 CUDA [nx, ns]) -> (list, row maxima or None): the numerator from
+    _matched_filter (taps = the de-meaned supports, no tail), then d4w_nmf_normalise_f32 in place, one launch per template pair
+    (x read once for both).  stats / next_head as _matched_filter (next_head: any container, see _nmf_head)."""
+    nx, ns = x.shape
+    next_head = _nmf_head(next_head, nx, max(len(t) for t in taps), x.device)
+    if stats is None:
+        stats = _row_stats_cached(x)                     # (the statistics the f-k filter deposited, when it ran last)
+    outs, _ = _matched_filter(x, taps, [0.0] * len(taps), stats=stats, next_head=next_head)
+    rmax = [] if want_row_max else None
+    with torch.cuda.device(x.device):
+        for i in range(0, len(taps), 2):
+            ms = [len(t) for t in taps[i:i + 2]]
+            ys, nn = outs[i:i + 2], norms[i:i + 2]
+            n_next = max(len(t) for t in taps) - 1 if next_head is not None else 0
+            rm = [torch.empty(nx, dtype=torch.float32, device=x.device) for _ in ys] if want_row_max else None
+            check(lib.d4w_nmf_normalise_f32(dev.ptr(x), nx, ns, dev.ptr(next_head) if n_next > 0 else None,
+                                            int(next_head.stride(0)) if n_next > 0 else 0, n_next, dev.ptr(stats[0]), dev.ptr(stats[1]),
+                                            len(ys), ms[0], ms[-1], nn[0], nn[-1], int(bool(center)), float(floor),
+                                            dev.out_ptr(ys[0]), dev.out_ptr(ys[1]) if len(ys) > 1 else None,
+                                            dev.ptr(rm[0]) if rm else None, dev.ptr(rm[1]) if rm and len(rm) > 1 else None,
+                                            dev.stream_ptr(x)))
+            if rm:
+                rmax.extend(rm)
+    return outs, rmax
+
+
+def _nmf_head(next_head, nx, longest, device):
+    """The continuation rows as the kernels read them in place: float32 CUDA [nx, >= longest - 1], unit stride along time."""
+    if next_head is None:
+        return None
+    if getattr(next_head, "ndim", 0) != 2 or next_head.shape[0] != nx or next_head.shape[1] < longest - 1:
+        raise ValueError("next_head must be [%d x >= %d] (the rows' continuation, longest support - 1 samples)" % (nx, longest - 1))
+    if not (dev.is_tensor(next_head) and next_head.is_cuda and next_head.dtype == torch.float32 and next_head.stride(1) == 1
+            and next_head.device == device):
+        next_head = dev.to_device_f32(next_head[:, :max(longest - 1, 1)], device)
+    return next_head
+
+
+def compute_nmf_correlograms(data, templates, center=True, floor=1e-6, next_head=None):
+    """Window-normalised matched filter of every row against several templates -> a list of [channel x time] correlation
+    COEFFICIENTS in [-1, 1], in the caller's container: lag k is the correlation of the template's support h (m samples,
+    de-meaned over the support) with the m samples under it, divided by |h'| and by the energy of THOSE samples --
+        nmf[k] = sum_n x'[k + n] h'[n] / (|h'| sqrt(V[k])),   V = S2 - S1^2 / m (center=True: the Pearson coefficient) or S2,
+    -- instead of by the row's loudest sample (compute_cross_correlogram, detect.py:157): a spike on a channel no longer buries
+    that channel's calls, a loud channel no longer sets everybody's threshold, and 0.6 means the same in every file.
+    floor: windows whose RMS is below floor x the row's max|x| give 0 (dropouts, constant stretches; a one-tap template gives
+    zeros).  next_head: [channel x >= longest support - 1] samples that continue the rows (the next file's head): the last
+    lags see them instead of zeros; they are normalised like the row's own samples.  Zeros behind the row count as data.
+    pick_times / pick_times_env take the result as it is; the two correlograms of a pair sit back to back (stacked_pair)."""
+    if getattr(data, "ndim", 0) != 2:
+        raise ValueError("data must be a 2-D [channel x time] array")
+    if not (np.isfinite(floor) and floor >= 0):
+        raise ValueError("floor must be finite and >= 0")
+    parts = [_nmf_parts(t) for t in templates]
+    if not parts:
+        return []
+    xd = dev.to_device_f32(data)
+    outs, _ = _nmf_device(xd, [h for h, _ in parts], [n for _, n in parts], center, floor, next_head=next_head)
+    return [dev.like_input(o, data) for o in outs]
+
+
+def compute_nmf_correlogram(data, template, center=True, floor=1e-6, next_head=None):
+    """compute_nmf_correlograms for one template."""
+    return compute_nmf_correlograms(data, [template], center=center, floor=floor, next_head=next_head)[0]
+
+
+# ---------------------------------------------------------------------------------------------
 # peak picking (d4w_find_peaks_f32; the envelope of the *_env variants is d4w_analytic_f32)
 # ---------------------------------------------------------------------------------------------
 class PickRows(collections.abc.Sequence):

@@ -29,19 +29,31 @@ from . import detect, dsp
 
 
 class FileStream:
-    def __init__(self, fs, fmin, fmax, templates=(), fk_mask=None, halo=1024, prev_tail=None, on_filtered=None):
+    def __init__(self, fs, fmin, fmax, templates=(), fk_mask=None, halo=1024, prev_tail=None, on_filtered=None, nmf=None):
         """fs, fmin, fmax: band-pass (dsp.bp_filt arguments); templates: full-length or support-only
         template vectors (detect.gen_template_fincall output) for the matched filter; fk_mask: f-k mask
         for one file's shape (any form dsp.fk_filter_filt accepts) or None to skip the f-k filter.
         prev_tail: the last `halo` raw samples of the file BEFORE the first one pushed (a stream that continues a
         record another process holds, e.g. the previous rank's last file); on_filtered(index, y): called as soon as a
-        file's band-passed (+ f-k filtered) version exists (the neighbour that needs its head can be served early)."""
+        file's band-passed (+ f-k filtered) version exists (the neighbour that needs its head can be served early).
+        nmf: None (default: the peak-normalised matched filter, results carry "correlograms") or True / a dict with `center`
+        and / or `floor` (detect.compute_nmf_correlograms' arguments): the window-normalised matched filter instead -- results
+        carry "nmf" and its "row_max" in place of "correlograms", the last lags completed from the next file's head alike."""
         self.fs, self.fmin, self.fmax = float(fs), float(fmin), float(fmax)
         self.halo = int(halo)
         self.taps = [detect._normalised_support(t) for t in templates]
         # DC tail of a zero-padded full-length template (detect.py:158), applied per file exactly as
         # detect.compute_cross_correlograms does (0 for support-only vectors)
         self.tail = [detect._tail_coef(t) for t in templates]
+        self.nmf = None
+        if nmf is not None and nmf is not False:
+            opts = {} if nmf is True else dict(nmf)
+            if set(opts) - {"center", "floor"}:
+                raise ValueError("nmf takes True or a dict with 'center' and / or 'floor', not %r" % (nmf,))
+            self.nmf = {"center": bool(opts.get("center", True)), "floor": float(opts.get("floor", 1e-6))}
+            parts = [detect._nmf_parts(t) for t in templates]
+            # the numerator's taps are the supports de-meaned over themselves, without the zero-padded templates' DC tail
+            self.taps, self.tail, self._norms = [h for h, _ in parts], [0.0] * len(parts), [n for _, n in parts]
         self.fk_mask = fk_mask
         self._raw = []          # raw files waiting for their right halo: [(index, tensor)]
         self._prev_tail = dev.to_device_f32(prev_tail) if prev_tail is not None else None   # last `halo` raw samples of the file before self._raw[0]
@@ -101,7 +113,10 @@ class FileStream:
         """Correlograms of filtered file `y`, its last lags completed with `next_head` (or cut short); stats = the row
         statistics of y when the f-k filter left them."""
         out = {"index": idx, "filtered": y}
-        if self.taps:
+        if self.taps and self.nmf is not None:
+            out["nmf"], out["row_max"] = detect._nmf_device(y, self.taps, self._norms, self.nmf["center"], self.nmf["floor"], stats=stats,
+                                                            next_head=next_head, want_row_max=True)
+        elif self.taps:
             # (a file without a successor -- the record's last -- gets its row maxima from the correlator's epilogue too)
             out["correlograms"], rmax = detect._matched_filter(y, self.taps, self.tail, stats=stats, next_head=next_head,
                                                                want_row_max=True)
@@ -112,7 +127,7 @@ class FileStream:
     # ------------------------------------------------------------------------------------------
     def push(self, block):
         """Next file ([channel x time], NumPy or CUDA tensor).  Returns the list of results that became
-        final (dicts with "index", "filtered" and "correlograms"), possibly empty.
+        final (dicts with "index", "filtered" and "correlograms" -- "nmf" with nmf=...), possibly empty.
 
         Lifetime of a pushed buffer: a float32 CUDA tensor is NOT copied -- file i is read in place by the work that
         push(i + 1) (or flush()) enqueues, and by nothing later (its last `halo` columns are copied out then).  A caller

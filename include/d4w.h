@@ -379,6 +379,29 @@ int d4w_xcorr_mm_tail_f32(const float* x, int nx, int ns, const float* xnext, in
                           int len0, int len1, double tail0, double tail1, float* y0, float* y1,
                           float* rowmax0, float* rowmax1, void* stream);
 
+/* Window-normalised matched filter (NMF, das4whales_amd/csrc/nmf.hip; no reference counterpart): a second pass that turns one
+ * or two correlograms y_t of the rows of x -- produced by any d4w_xcorr_*_f32 with the SAME mean / maxabs (and the same
+ * continuation), taps h'_t de-meaned over their support, no tail -- into correlation coefficients, in place:
+ *   x'[i] = (x[c][i] - mean[c]) / maxabs[c] for i < ns, the same of xnext[c][i - ns] for ns <= i < ns + n_next, 0 beyond
+ *   S1[k] = sum_{n < len_t} x'[k + n],  S2[k] = sum_{n < len_t} x'[k + n]^2,  V[k] = S2 - S1^2 / len_t (center = 1) or S2 (0)
+ *   y_t[c][k] <- y_t[c][k] / (norm_t sqrt(V[k]))  where V[k] > floor^2 len_t,  0 elsewhere          (|.| <= 1 up to rounding)
+ * norm_t = |h'_t|_2 from the host (0: a template without shape -- every lag 0); floor: the smallest window RMS, relative to
+ * the row's max|x|, that is still divided by (dropouts, constant stretches and a one-tap window give 0, not rounding noise
+ * over rounding noise); a row with maxabs = 0 gives zeros.  The windowed sums are float64 (sliding, re-anchored every 8 lags
+ * from float64 sums of 8-sample runs), the final scale float32.  x is read once for both templates (len0 != len1 allowed),
+ * every correlogram read and written once: 20 B per sample for a pair.  rowmax_t (DEVICE [nx], NULL or both with ntpl = 2):
+ * max over the lags of the NORMALISED rows.  Supports <= d4w_nmf_max_support() = 7936 (>= d4w_xcorr_mm_max_support());
+ * d4w_nmf_tile(): the lags one workgroup takes (what the tests size their row ends by).
+ * Errors: D4W_EINVAL for a NULL x / y0 / mean / maxabs (y1 with ntpl = 2), nx or ns < 1, ntpl other than 1 or 2, a support
+ * outside 1..d4w_nmf_max_support(), a norm or floor that is negative or not finite, center other than 0 / 1, n_next < 0 or
+ * > ld_next, one rowmax of a pair without the other. */
+int d4w_nmf_max_support(void);
+int d4w_nmf_tile(void);
+int d4w_nmf_normalise_f32(const float* x, int nx, int ns, const float* xnext, int ld_next, int n_next,
+                          const double* mean, const float* maxabs, int ntpl, int len0, int len1,
+                          double norm0, double norm1, int center, double floor, float* y0, float* y1,
+                          float* rowmax0, float* rowmax1, void* stream);
+
 /* Zero-phase FIR along time by overlap-save FFT blocks -- the INTERIOR of dsp.bp_filt / scipy.signal.sosfiltfilt
  * (dsp.py:859-880): away from the row ends a zero-phase IIR filter is the convolution with its two-sided response
  * g = h * h(-t), truncated at half width K where it has decayed below the tolerance (north star: "overlap-save FIR").
