@@ -120,6 +120,10 @@ def _load():
         "d4w_nmf_normalise_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                           ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
+        "d4w_semblance_limits": (c_int, [P(c_int), P(c_int), P(c_int), P(c_int)]),
+        "d4w_semblance_tile": (c_int, [P(c_int), P(c_int)]),
+        "d4w_semblance_f32": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
         "d4w_xcorr_fft_max_support": (c_int, []),
         "d4w_xcorr_fft_ws_bytes": (ctypes.c_size_t, []),
         "d4w_xcorr_fft_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -577,6 +577,107 @@ def compute_nmf_correlogram(data, template, center=True, floor=1e-6, next_head=N
 
 
 # ---------------------------------------------------------------------------------------------
+# local slant-stack semblance (no reference counterpart; DESIGN.md 3.3b, csrc/semblance.hip)
+# ---------------------------------------------------------------------------------------------
+def semblance_limits():
+    """The largest half aperture M, number of trial slownesses, half window H and |delay| in samples local_semblance takes."""
+    import ctypes
+    v = [ctypes.c_int() for _ in range(4)]
+    check(lib.d4w_semblance_limits(*[ctypes.byref(c) for c in v]))
+    return {"half_aperture": v[0].value, "slownesses": v[1].value, "half_window": v[2].value, "abs_delay": v[3].value}
+
+
+def slowness_delays(slowness, dx, fs, half_aperture):
+    """Delay table of plane arrivals for local_semblance: float64 [np, 2M + 1] with d[j, m] = m * slowness[j] * dx * fs samples,
+    m = -M .. M.  slowness: signed apparent slownesses in s/m (positive: the arrival is later at higher channel numbers);
+    dx: spacing of the selected channels in metres; fs: sampling rate in Hz; half_aperture: M."""
+    s = _host_vec(slowness)
+    M = int(half_aperture)
+    if s.size < 1 or not np.all(np.isfinite(s)):
+        raise ValueError("slowness must be a non-empty 1-D list of finite values (s/m)")
+    if M != half_aperture or M < 1:
+        raise ValueError("half_aperture must be an integer >= 1")
+    if not (np.isfinite(dx) and dx > 0 and np.isfinite(fs) and fs > 0):
+        raise ValueError("dx and fs must be finite and > 0")
+    m = np.arange(-M, M + 1, dtype=np.float64)
+    return m[None, :] * s[:, None] * float(dx) * float(fs)
+
+
+def _split_delays(delays):
+    """k = floor(d), f = float32(d - k); a fraction that rounds to 1.0f is carried into k (include/d4w.h)."""
+    k = np.floor(delays)
+    f = (delays - k).astype(np.float32)
+    carry = f >= np.float32(1.0)
+    return np.where(carry, k + 1, k), np.where(carry, np.float32(0.0), f).astype(np.float32)
+
+
+def local_semblance(data, delays, half_window, weights=None, return_all=False):
+    """Local slant-stack semblance of a [channel x time] block -> (coh, idx), or (coh, idx, cube) with return_all=True: for every
+    channel c and sample t the coherence in [0, 1] of the 2M + 1 neighbouring channels along each of np trial moveouts, the
+    largest of them (coh, float32) and the smallest trial that attains it (idx, uint8); cube is every trial's S, float32
+    [np, channel, time].  The measure does not depend on amplitude: one threshold serves every channel and file.
+        delays: float64 [np, 2M + 1] in samples, slowness_delays(...) or any table whose centre column is 0 (curved moveouts
+            are allowed); d is split into k = floor(d) and a float32 fraction f.
+        X(c, u) = data[c, u] inside the record, 0 outside; a neighbour c + m outside the block or of weight 0 is absent.
+        xi = v0 + f (v1 - v0), v0 = X(c + m, tau + k), v1 = X(c + m, tau + k + 1);  b = sum_m w xi, e = sum_m w xi^2, W = sum_m w
+        S_j[c, t] = sum_tau b^2 / (W sum_tau e) over tau in [t - H, t + H] inside the record; 0 where W sum e = 0
+    half_window: H >= 0.  weights: [2M + 1] >= 0 with a centre > 0 (default ones).  float32 throughout; window sums only add
+    their terms (no running sums), so two runs agree bit for bit.  Non-finite samples give an unspecified result.
+    With the slowness list s that made the table: s[idx] is the apparent slowness (its sign: which side of a call's apex;
+    the sign change: the closest point of approach), 1 / s[idx] the apparent speed.  Works on strain, on f-k filtered strain
+    and on matched-filter correlograms alike.  Results come in the caller's container (NumPy array or CUDA tensor).
+    Limits (semblance_limits()): M <= 16, np <= 64, H <= 64, |delay| <= 64 samples; beyond them ValueError."""
+    if getattr(data, "ndim", 0) != 2 or data.shape[0] < 1 or data.shape[1] < 1:
+        raise ValueError("data must be a 2-D [channel x time] array of at least one channel and one sample")
+    lim = semblance_limits()
+    d = np.asarray(delays.detach().cpu().numpy() if dev.is_tensor(delays) else delays, dtype=np.float64)
+    if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] < 3 or d.shape[1] % 2 == 0:
+        raise ValueError("delays must be a 2-D [np x 2M + 1] table with M >= 1")
+    npj, n = d.shape
+    M = (n - 1) // 2
+    if M > lim["half_aperture"]:
+        raise ValueError("half aperture %d exceeds the limit of %d channels" % (M, lim["half_aperture"]))
+    if npj > lim["slownesses"]:
+        raise ValueError("%d trial slownesses exceed the limit of %d" % (npj, lim["slownesses"]))
+    if not np.all(np.isfinite(d)) or np.max(np.abs(d)) > lim["abs_delay"]:
+        raise ValueError("delays must be finite and within +-%d samples" % lim["abs_delay"])
+    if np.any(d[:, M] != 0):
+        raise ValueError("the centre column of delays must be 0")
+    H = int(half_window)
+    if H != half_window or H < 0 or H > lim["half_window"]:
+        raise ValueError("half_window must be an integer in 0..%d" % lim["half_window"])
+    w = np.ones(n, dtype=np.float32) if weights is None else np.asarray(_host_vec(weights), dtype=np.float32)
+    if w.shape != (n,):
+        raise ValueError("weights must have 2M + 1 = %d entries" % n)
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("weights must be finite and >= 0")
+    if not w[M] > 0:
+        raise ValueError("the centre weight must be > 0")
+    k, f = _split_delays(d)
+    k = np.ascontiguousarray(k, dtype=np.int32)
+    f = np.ascontiguousarray(f, dtype=np.float32)
+    w = np.ascontiguousarray(w)
+    if dev.is_tensor(data) and data.is_cuda and data.dtype == torch.float32 and data.stride(1) == 1 and data.stride(0) >= data.shape[1]:
+        xd = data                                        # a column-sliced view is read in place (row pitch)
+    else:
+        xd = dev.to_device_f32(data)
+    nx, ns = xd.shape
+    coh = torch.empty((nx, ns), dtype=torch.float32, device=xd.device)
+    idx = torch.empty((nx, ns), dtype=torch.uint8, device=xd.device)
+    cube = torch.empty((npj, nx, ns), dtype=torch.float32, device=xd.device) if return_all else None
+    with torch.cuda.device(xd.device):
+        check(lib.d4w_semblance_f32(dev.ptr(xd), int(xd.stride(0)), nx, ns, k.ctypes.data, f.ctypes.data, npj, M, w.ctypes.data, H,
+                                    dev.out_ptr(coh), dev.out_ptr(idx), dev.out_ptr(cube) if return_all else None, dev.stream_ptr(xd)))
+    if dev.is_tensor(data):
+        outs = [o if data.is_cuda else o.to(data.device) for o in ((coh, idx, cube) if return_all else (coh, idx))]
+    else:
+        outs = [dev.like_input(coh, data), idx.cpu().numpy()]
+        if return_all:
+            outs.append(dev.like_input(cube, data))
+    return tuple(outs)
+
+
+# ---------------------------------------------------------------------------------------------
 # peak picking (d4w_find_peaks_f32; the envelope of the *_env variants is d4w_analytic_f32)
 # ---------------------------------------------------------------------------------------------
 class PickRows(collections.abc.Sequence):

@@ -402,6 +402,29 @@ int d4w_nmf_normalise_f32(const float* x, int nx, int ns, const float* xnext, in
                           double norm0, double norm1, int center, double floor, float* y0, float* y1,
                           float* rowmax0, float* rowmax1, void* stream);
 
+/* Local slant-stack semblance (das4whales_amd/csrc/semblance.hip; no reference counterpart): per channel and
+ * sample the coherence of the 2M + 1 neighbouring channels along np trial moveouts, and the trial that maximises it.
+ *   x = DEVICE [nx][pitch] float32, pitch in ELEMENTS (pitch >= ns: a column-sliced view is read in place).
+ *   k, f = HOST [np][2M + 1]: the delay of trial j at neighbour m - M, split as floor(d) and float32(d - floor(d)) (a fraction
+ *     that rounds to 1 carried into k); column M, the centre channel, is (0, 0).  w = HOST [2M + 1] weights >= 0, centre > 0.
+ *   X(c, u) = x[c][u] for 0 <= u < ns, 0 elsewhere; a neighbour c + m outside [0, nx) or with w_m = 0 is absent.  Over the
+ *   present neighbours in increasing m, float32, one fmaf per term:
+ *     xi = v0 + f (v1 - v0), v0 = X(c + m, tau + k), v1 = X(c + m, tau + k + 1);  b = sum w xi, e = sum w xi^2, W = sum w
+ *     N[t] = sum b^2, E[t] = sum e over tau in [max(0, t - H), min(ns - 1, t + H)];  S_j[c][t] = N / (W E) if W E > 0 else 0
+ *   coh = DEVICE [nx][ns] float32 max_j S_j; idx = DEVICE [nx][ns] uint8, the smallest j attaining it; cube = DEVICE
+ *   [np][nx][ns] float32 of every S_j, or NULL.  Window sums only ever add their non-negative terms in one fixed order (no
+ *   running or prefix sums, no atomics): run-to-run bit-identical, and exact scaling of x by a power of two changes no bit.
+ *   Non-finite input gives an unspecified result.  The table is uploaded in stream order for the call alone.
+ * d4w_semblance_limits: the largest M (16), np (64), H (64) and |delay| in samples (64) a call takes.
+ * d4w_semblance_tile: the output channels x samples one workgroup owns (what the tests size their shapes by).
+ * Errors: D4W_EINVAL for a NULL required pointer, nx or ns < 1, pitch < ns, M, np or H outside the limits, a delay beyond
+ *   +-64 samples, a fraction outside [0, 1), a non-zero centre delay, a weight that is negative or not finite, a centre
+ *   weight of 0. */
+int d4w_semblance_limits(int* max_half_aperture, int* max_slownesses, int* max_half_window, int* max_abs_delay);
+int d4w_semblance_tile(int* channels, int* samples);
+int d4w_semblance_f32(const float* x, int64_t pitch, int nx, int ns, const int32_t* k, const float* f, int np, int M,
+                      const float* w, int H, float* coh, uint8_t* idx, float* cube /* or NULL */, void* stream);
+
 /* Zero-phase FIR along time by overlap-save FFT blocks -- the INTERIOR of dsp.bp_filt / scipy.signal.sosfiltfilt
  * (dsp.py:859-880): away from the row ends a zero-phase IIR filter is the convolution with its two-sided response
  * g = h * h(-t), truncated at half width K where it has decayed below the tolerance (north star: "overlap-save FIR").
