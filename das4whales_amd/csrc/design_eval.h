@@ -1,6 +1,6 @@
 // Closed-form point evaluation of the reference's f-k mask designs on the fftshift-ed (k, f) grid -- shared by the
 // dense design kernel (design.hip) and the fold that writes a design straight into a plan's pass-B order without a
-// dense mask in between (fk_filter.hip, d4w_fk_set_mask_design_f32).  Reference: dsp.py:85-454, 457-702, 883-953.
+// dense mask in between (fk_filter.hip: d4w_fk_set_mask_design_f32; fk_dist.hip: the slab fold).  Reference: dsp.py:85-454, 457-702, 883-953.
 #pragma once
 #include "d4w_internal.h"
 

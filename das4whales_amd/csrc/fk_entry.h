@@ -1,4 +1,4 @@
-// Types shared by the f-k filter's planner (fk_filter.hip) and by shape configurations compiled on demand
+// Types shared by the f-k filter's planners (fk_filter.hip, fk_dist.hip; fk_plan.h) and by shape configurations compiled on demand
 // (das4whales_amd/fkjit.py): the kernel argument blocks, the pass kernels of fk_fast.h and the table entry that
 // names one instantiated shape.
 #pragma once

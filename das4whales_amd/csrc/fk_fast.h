@@ -13,7 +13,7 @@
 //     four-step twiddles W_nx^(c2 kc1) are wave-uniform scalar loads;
 //   * persistent workgroups prefetch the next tile's butterfly inputs straight into registers
 //     while the current tile is in its LDS phase.
-// Instantiated for the shapes listed in fk_filter.hip (kFastShapes); any other shape runs the
+// Instantiated for the shapes listed in fk_filter.hip (fast_shapes()); any other shape runs the
 // generic kernels.
 #pragma once
 #include "fft_lds.h"

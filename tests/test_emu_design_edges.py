@@ -1,5 +1,5 @@
 """The cases of tests/design_cases.py on the CPU emulator build of design.hip / design_eval.h / the closed-form fold of
-fk_filter.hip, against the float64 oracle: what tests/test_design_edges_gpu.py runs on gfx950, so that a failure there can
+fk_filter.hip (fk_dist.hip for the slab fold), against the float64 oracle: what tests/test_design_edges_gpu.py runs on gfx950, so that a failure there can
 be told from a failure of the C code."""
 import ctypes
 

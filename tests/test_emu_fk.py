@@ -68,7 +68,7 @@ def test_in_place(emu, golden):
 
 @pytest.mark.parametrize("nx,ns", [(18, 48), (8, 480), (100, 600), (154, 48), (1102, 48)])
 def test_shape_specialised_kernels(emu, nx, ns):
-    """Shapes in fk_filter.hip's kFastShapes run the fat-stage register-FFT kernels (fk_fast.h);
+    """Shapes in fk_filter.hip's fast_shapes() run the fat-stage register-FFT kernels (fk_fast.h);
     opts[0] = -1 forces the generic passes on the same shape: both must match the oracle."""
     rng = np.random.default_rng(nx + ns)
     x = rng.standard_normal((nx, ns))

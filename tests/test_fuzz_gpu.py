@@ -263,7 +263,7 @@ def test_spectrogram_windows_with_large_prime_factors(dw):
 
 def test_any_channel_count(dw):
     """Channel counts whose part with prime factors > 31 exceeds 4096 (the LDS Bluestein tile of pass C): the plan runs the
-    global-memory Bluestein form of the channel transform (fk_filter.hip: fkd_bz_*) -- numpy.fft.fft2 (dsp.py:748) takes any
+    global-memory Bluestein form of the channel transform (fk_dist.hip: fkd_bz_*) -- numpy.fft.fft2 (dsp.py:748) takes any
     shape.  Dense, designed and fk_filt masks, taper, in several scratch chunks."""
     rng = np.random.default_rng(111 + SEED)
     for nx, ns in ((4099, 64), (2 * 5003, 240), (10007, 1200)):
