@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 
 from oracle import d4w_oracle as orc
+from tests import fk_dist_cases as fc
 from tests.emu_util import load_emu, vp
+from tests.fk_dist_cases import Rank
 
 TOL = 1e-5
 
@@ -22,62 +24,13 @@ def rel(y, ref):
     return np.max(np.abs(y - ref)) / np.max(np.abs(ref))
 
 
-class Rank:
-    def __init__(self, lib, nx, ns, world, rank):
-        self.lib = lib
-        self.h = ctypes.c_void_p()
-        assert lib.d4w_fkd_plan_create(nx, ns, world, rank, ctypes.byref(self.h)) == 0, lib.d4w_last_error()
-        info = (ctypes.c_int * 12)()
-        assert lib.d4w_fkd_plan_info(self.h, info) == 0
-        (_, _, _, _, self.a, self.b, self.N1, self.N2, self.nq, self.C1, self.C2, _) = list(info)
-        own = (ctypes.c_int * self.N1)()
-        assert lib.d4w_fkd_plan_q1_owner(self.h, own) == 0
-        self.owner = np.array(list(own))
-
-    def close(self):
-        self.lib.d4w_fkd_plan_destroy(self.h)
-
-
 def fk_sharded_emu(lib, x, mask, world, taper=False, setter=None):
-    nx, ns = x.shape
-    M = ns // 2
-    ranks = [Rank(lib, nx, ns, world, r) for r in range(world)]
-    N1, N2 = ranks[0].N1, ranks[0].N2
-    owner = ranks[0].owner
-    assert all(np.array_equal(rk.owner, owner) for rk in ranks)          # every rank derives the same map
-    assert ranks[0].a == 0 and ranks[-1].b == nx and all(ranks[i].b == ranks[i + 1].a for i in range(world - 1))
-    assert sorted(owner.tolist()) == sorted(sum(([r] * ranks[r].nq for r in range(world)), []))
-    mf = np.ascontiguousarray(mask, dtype=np.float32)
-    xf = np.ascontiguousarray(x, dtype=np.float32)
-    z = []
-    for rk in ranks:
-        if setter is not None:
-            setter(rk)
-        else:
-            assert lib.d4w_fkd_set_mask_dense_f32(rk.h, vp(mf), None) == 0
-        xl = np.ascontiguousarray(xf[rk.a:rk.b])
-        zl = np.empty((rk.b - rk.a, N1, N2, 2), dtype=np.float32)
-        assert lib.d4w_fkd_time_fwd_f32(rk.h, vp(xl), vp(zl), int(taper), None) == 0, lib.d4w_last_error()
-        z.append(zl)
-    # all-to-all: sub-row q1 of every channel -> rank owner[q1]; receiver concatenates in rank order
-    qidx = [np.nonzero(owner == s)[0] for s in range(world)]
-    slabs = [np.ascontiguousarray(np.concatenate([z[r][:, qidx[s]] for r in range(world)], axis=0))
-             for s in range(world)]
-    for s, rk in enumerate(ranks):
-        assert slabs[s].shape == (nx, rk.nq, N2, 2)
-        assert lib.d4w_fkd_chan_apply_f32(rk.h, vp(slabs[s]) if rk.nq else None, None) == 0, lib.d4w_last_error()
-    # all-to-all back
-    y = np.empty((nx, ns), dtype=np.float32)
-    for r, rk in enumerate(ranks):
-        zl = z[r]
-        for s in range(world):
-            zl[:, qidx[s]] = slabs[s][rk.a:rk.b]
-        assert lib.d4w_fkd_time_inv_f32(rk.h, vp(zl), None) == 0, lib.d4w_last_error()
-        y[rk.a:rk.b] = zl.reshape(rk.b - rk.a, ns)
-    for rk in ranks:
-        rk.close()
-    assert M == N1 * N2
-    return y
+    return fc.fk_sharded(fc.EmuBackend(lib), x, mask, world, taper=taper, setter=setter)
+
+
+def fk_sharded_packed_emu(lib, x, mask, world, taper=False):
+    # one chunk count per world here (tests/test_fk_dist_ranks_gpu.py runs 1, 2 and 3 for every case: milliseconds there)
+    return fc.fk_sharded_packed(fc.EmuBackend(lib), x, mask, world, taper=taper, nchunks=({1: 2, 2: 3, 3: 1}.get(world, 2),))
 
 
 @pytest.mark.parametrize("world", [1, 2, 3])
@@ -174,6 +127,18 @@ def test_dist_record_length_with_large_prime_factor(emu, nx, ns, world):
     assert rel(fk_sharded_emu(emu, x, m, world, taper=True), orc.fk_filter_filt(x, m, tapering=True)) < TOL
 
 
+@pytest.mark.parametrize("nx,ns,world", [(12, 74, 1), (10, 2 * 41 * 3, 2), (37, 2 * 43, 3)])
+def test_dist_time_bluestein_in_row_chunks(emu, nx, ns, world, monkeypatch):
+    """The same with D4W_FKD_BT_CHUNK=3 rows per pass through the time-axis Bluestein scratch: 12 rows in 4 chunks, blocks of 5
+    rows in 2 chunks with a ragged second one, blocks of 13, 12 and 12 rows with a ragged last chunk on rank 0."""
+    monkeypatch.setenv("D4W_FKD_BT_CHUNK", "3")
+    rng = np.random.default_rng(ns + world)
+    x = rng.standard_normal((nx, ns))
+    m = rng.uniform(0, 1, (nx, ns))
+    assert rel(fk_sharded_emu(emu, x, m, world), orc.fk_filter_filt(x, m)) < TOL
+    assert rel(fk_sharded_emu(emu, x, m, world, taper=True), orc.fk_filter_filt(x, m, tapering=True)) < TOL
+
+
 def test_dist_plan_errors(emu):
     h = ctypes.c_void_p()
     assert emu.d4w_fkd_plan_create(40, 481, 2, 0, ctypes.byref(h)) == -1
@@ -181,67 +146,13 @@ def test_dist_plan_errors(emu):
     assert emu.d4w_fkd_plan_create(4, 480, 8, 0, ctypes.byref(h)) == -1       # more ranks than channels
 
 
-def fk_sharded_packed_emu(lib, x, mask, world, taper=False):
-    """The PACKED protocol of include/d4w.h (shapes with specialised kernels): the time phase writes the send buffer,
-    destination rank major; the exchanges are plain concatenations -- no index packing anywhere."""
-    nx, ns = x.shape
-    ranks = [Rank(lib, nx, ns, world, r) for r in range(world)]
-    assert all(lib.d4w_fkd_plan_is_packed(rk.h) == 1 for rk in ranks)
-    N1, N2 = ranks[0].N1, ranks[0].N2
-    owner = ranks[0].owner
-    assert all(np.array_equal(rk.owner, owner) for rk in ranks)
-    nq = [int(np.sum(owner == s)) for s in range(world)]
-    assert [rk.nq for rk in ranks] == nq
-    mf = np.ascontiguousarray(mask, dtype=np.float32)
-    xf = np.ascontiguousarray(x, dtype=np.float32)
-    send = []
-    for rk in ranks:
-        assert lib.d4w_fkd_set_mask_dense_f32(rk.h, vp(mf), None) == 0, lib.d4w_last_error()
-        nxl = rk.b - rk.a
-        buf = np.full(nxl * N1 * N2 * 2, np.nan, dtype=np.float32)
-        xl = np.ascontiguousarray(xf[rk.a:rk.b])
-        assert lib.d4w_fkd_time_fwd_packed_f32(rk.h, vp(xl), vp(buf), int(taper), None) == 0, lib.d4w_last_error()
-        assert not np.isnan(buf).any()
-        send.append(buf)
-    # all_to_all_single: rank r's block for s = elements [off_r[s], off_r[s+1])
-    def splits(r):
-        nxl = ranks[r].b - ranks[r].a
-        return np.concatenate(([0], np.cumsum([nxl * nq[s] * N2 * 2 for s in range(world)])))
-    slabs = []
-    for s, rk in enumerate(ranks):
-        parts = [send[r][splits(r)[s]:splits(r)[s + 1]] for r in range(world)]
-        slab = np.ascontiguousarray(np.concatenate(parts))
-        assert slab.size == nx * nq[s] * N2 * 2
-        assert lib.d4w_fkd_chan_apply_f32(rk.h, vp(slab) if nq[s] else None, None) == 0, lib.d4w_last_error()
-        slabs.append(slab)
-    y = np.empty((nx, ns), dtype=np.float32)
-    for r, rk in enumerate(ranks):
-        nxl = rk.b - rk.a
-        parts = [slabs[s][rk.a * nq[s] * N2 * 2:rk.b * nq[s] * N2 * 2] for s in range(world)]
-        back = np.ascontiguousarray(np.concatenate(parts))
-        yl = np.full((nxl, ns), np.nan, dtype=np.float32)
-        assert lib.d4w_fkd_time_inv_packed_f32(rk.h, vp(back), vp(yl), None) == 0, lib.d4w_last_error()
-        y[rk.a:rk.b] = yl
-        # the same pass with the row statistics in its epilogue, in two row chunks
-        ys = np.full((nxl, ns), np.nan, dtype=np.float32)
-        mean, mx = np.zeros(nxl, np.float64), np.zeros(nxl, np.float32)          # float64 row means (include/d4w.h)
-        cut = min(nxl, rk.C1 * max(1, (nxl // rk.C1) // 2))
-        for l0, l1 in ((0, cut), (cut, nxl)):
-            if l1 > l0:
-                assert lib.d4w_fkd_time_inv_packed_rows_stats_f32(rk.h, vp(back), vp(ys), l0, l1, vp(mean), vp(mx), None) == 0, lib.d4w_last_error()
-        assert np.array_equal(ys, yl)
-        assert np.allclose(mx, np.abs(yl).max(axis=1), rtol=1e-6)
-        assert np.max(np.abs(mean - yl.astype(np.float64).mean(axis=1))) < 1e-6 * max(np.abs(yl).max(), 1e-30)
-    for rk in ranks:
-        rk.close()
-    return y
-
-
-@pytest.mark.parametrize("nx,ns", [(18, 48), (100, 600), (8, 480)])
+@pytest.mark.parametrize("nx,ns", [(18, 48), (100, 600), (8, 480), (154, 48), (1102, 48)])
 @pytest.mark.parametrize("world", [1, 2, 3, 5])
 def test_dist_packed_specialised_shapes(emu, nx, ns, world):
     """Shapes with specialised kernels run the packed distributed plan (pass kernels of fk_fast.h in their slab modes):
-    same filter as the oracle for dense masks, masks with dead wavenumber rows, with the taper, uneven blocks."""
+    same filter as the oracle for dense masks, masks with dead wavenumber rows, with the taper, uneven blocks (154 x 48:
+    the radix-7 and radix-11 butterflies, 1102 x 48: radices 19 and 29).  The harness also runs both time phases through
+    their row-chunked entry points, in 1, 2 or 3 chunks (tests/fk_dist_cases.py)."""
     if world > nx:
         pytest.skip("more ranks than channels")
     rng = np.random.default_rng(nx * 7 + ns + world)

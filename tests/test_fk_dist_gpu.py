@@ -85,6 +85,30 @@ def test_sharded_plan_of_a_shape_without_built_in_kernels(pg):
         del plan
 
 
+def test_sharded_apply_with_row_statistics(pg):
+    """ShardedFkPlan.apply(stats=True) (packed plan, 100 x 600): the last pass's epilogue leaves max|.| and the float64 mean of
+    every filtered row -- atomics over the row's tiles -- and writes the same rows as the pass without it."""
+    from das4whales_amd import shard
+    nx, ns = 100, 600
+    rng = np.random.default_rng(11)
+    xh, mh = rng.standard_normal((nx, ns)), rng.uniform(0, 1, (nx, ns))
+    x = torch.from_numpy(xh).float().cuda()
+    plan = shard.ShardedFkPlan(nx, ns)
+    assert plan.packed
+    plan.set_mask(torch.from_numpy(mh).float().cuda())
+    y, mean, mx = plan.apply(x, stats=True)
+    assert mean.dtype == torch.float64 and mx.dtype == torch.float32 and mean.shape == mx.shape == (nx,)
+    err = rel(y.cpu().numpy(), orc.fk_filter_filt(xh, mh))
+    print("sharded 100x600 with row statistics vs oracle: %.3e" % err)
+    assert err < TOL
+    assert torch.equal(mx, y.abs().amax(1))
+    dm = float((mean - y.double().mean(1)).abs().max())
+    print("row mean error / max|y|: %.3e" % (dm / float(y.abs().max())))
+    assert dm < 1e-6 * float(y.abs().max())
+    assert torch.equal(plan.apply(x), y)
+    del plan
+
+
 def test_sharded_bench_shape_identity(pg):
     """20 000 x 120 000 (BASELINE configs[3] block on one rank): an all-ones mask returns the input."""
     from das4whales_amd import shard
