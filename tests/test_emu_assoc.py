@@ -220,6 +220,26 @@ def test_select_ties_go_to_the_smaller_k(lib):
     assert list(chosen) == [-1, -1, -1] and rec[0, 3] == 0 and np.isnan(fg[0, 3]) and np.all(assigned == 1)
 
 
+def emu_rounds(lib, table, cable, xs, ys, z, lo, dt, nbins, min_picks, max_calls, after_round=None):
+    """The greedy loop as loc.associate_picks enqueues it: the vote, then best / select / subtract `max_calls` times with
+    the stop flag handed on.  After every round the accumulator must be the restatement's vote of the picks not assigned so
+    far, and after_round(c, votes, state, rec, assigned, Ti) may look further.  Returns (state, rec, assigned, Ti, fg, votes)."""
+    nch = len(cable)
+    votes = emu_vote(lib, table, cable, xs, ys, z, lo, dt, nbins)
+    state, rec = np.zeros(2, dtype=np.int32), np.zeros((max_calls, 4), dtype=np.int32)
+    assigned, Ti = np.zeros(table.shape[1], dtype=np.int32), np.full((max_calls, nch), 7.0)
+    fg = np.full((max_calls, 4), 7.0)
+    for c in range(max_calls):
+        emu_best(lib, votes, min_picks, call=c, state=state, rec=rec)
+        chosen, _, _ = emu_select(lib, table, cable, xs, ys, z, lo, dt, nbins, c, state, rec, assigned, Ti, fg=fg)
+        emu_vote(lib, table, cable, xs, ys, z, lo, dt, nbins, idx=chosen, sign=-1, votes=votes, stop=state)
+        left, _, _ = ka.vote(table[:, assigned == 0], FS, cable, C0, xs, ys, z, dt, layout=(lo, nbins))
+        assert np.array_equal(votes, left), c                # the invariant, after every round
+        if after_round is not None:
+            after_round(c, votes, state, rec, assigned, Ti)
+    return state, rec, assigned, Ti, fg, votes
+
+
 @pytest.mark.parametrize("kind,seed", [("bent", 21), ("line", 22)])
 def test_rounds_against_the_restatement(lib, kind, seed):
     cable, table, _ = ka.scene(kind, 400, seed=seed)
@@ -227,16 +247,7 @@ def test_rounds_against_the_restatement(lib, kind, seed):
     Ti_ref, ref = ka.associate(table, FS, cable, C0, xs, ys, z, 0.5, 60, max_calls=8)
     assert ref["margin"] >= ka.MARGIN and 3 <= len(Ti_ref) < 8
     lo, nbins = ref["edges"][0], len(ref["edges"]) - 1
-    votes = emu_vote(lib, table, cable, xs, ys, z, lo, 0.5, nbins)
-    state, rec = np.zeros(2, dtype=np.int32), np.zeros((8, 4), dtype=np.int32)
-    assigned, Ti = np.zeros(table.shape[1], dtype=np.int32), np.full((8, 400), 7.0)
-    fg = np.full((8, 4), 7.0)
-    for c in range(8):
-        emu_best(lib, votes, 60, call=c, state=state, rec=rec)
-        chosen, _, _ = emu_select(lib, table, cable, xs, ys, z, lo, 0.5, nbins, c, state, rec, assigned, Ti, fg=fg)
-        emu_vote(lib, table, cable, xs, ys, z, lo, 0.5, nbins, idx=chosen, sign=-1, votes=votes, stop=state)
-        left, _, _ = ka.vote(table[:, assigned == 0], FS, cable, C0, xs, ys, z, 0.5, layout=(lo, nbins))
-        assert np.array_equal(votes, left), c                # the invariant, after every round
+    state, rec, assigned, Ti, fg, votes = emu_rounds(lib, table, cable, xs, ys, z, lo, 0.5, nbins, 60, 8)
     n = len(Ti_ref)
     assert list(state) == [1, n]
     assert np.array_equal(Ti[:n], Ti_ref, equal_nan=True) and np.array_equal(assigned, ref["assigned"])
