@@ -4,7 +4,9 @@ The nine reference functions keep their names, parameter names and defaults.  Th
 the misfit grid run in csrc/loc.hip (float64); `solve_lq_batch`, `misfit_grid` and `first_guess_grid` are the batched forms
 the reference does not have; `vote_grid` and `associate_picks` (csrc/assoc.hip) turn the picks of detect.pick_times* into
 the [ncalls x channel] arrival times these take; `delay_table`, `stack_grid`, `stack_best`, `arrivals_near` and
-`locate_stack` (csrc/stack.hip) get them from the envelopes themselves by a delay-and-sum over the same grid.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
+`locate_stack` (csrc/stack.hip) get them from the envelopes themselves by a delay-and-sum over the same grid; `beam_delays` and
+`beamform` (csrc/beam.hip) close the chain with the waveform of a located call, the strain of all channels advanced by their
+travel times from the position and summed.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
 same device and stream.  The four small per-channel helpers (distances, radii, angles) are host float64 arithmetic for NumPy input, like the
 index arithmetic of the other namespaces; for tensors they stay on the device.
 
@@ -737,3 +739,191 @@ def locate_stack(env, fs, cable_pos, c0, xs, ys, z, threshold, halfwidth, pick_t
         if return_stack:
             info.update(stack=stack, peak=peak, best_node=best_node)
     return _out(Ti, as_tensor), {k: _out(v, as_tensor) for k, v in info.items()}
+
+
+# ------------------------------------------------------------------------------------------
+# beyond the reference: delay-and-sum beam of the strain toward located calls (csrc/beam.hip)
+# ------------------------------------------------------------------------------------------
+def beam_limits():
+    """(largest ncalls of a call, largest length, channels per summation segment, samples per workgroup) of the beam kernel."""
+    import ctypes
+    a, b, s, t = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib.d4w_beam_limits(ctypes.byref(a), ctypes.byref(b), ctypes.byref(s)))
+    _lib.check(_lib.lib.d4w_beam_tile(ctypes.byref(t)))
+    return a.value, b.value, s.value, t.value
+
+
+def _positions(pos, device):
+    p = _f64(pos, device)
+    return p.reshape(1, -1) if p.dim() == 1 else p
+
+
+def _beam_delays(cable, c0, fs, p, rounded):
+    ncalls, nch = p.shape[0], cable.shape[0]
+    if rounded:
+        r = torch.empty((ncalls, nch), dtype=torch.int32, device=cable.device)
+        if ncalls:
+            _lib.check(_lib.lib.d4w_beam_delays(dev.ptr(cable), nch, c0, fs, dev.ptr(p), ncalls, None, None, dev.out_ptr(r), dev.stream_ptr(cable)))
+        return r
+    k = torch.empty((ncalls, nch), dtype=torch.int32, device=cable.device)
+    f = torch.empty((ncalls, nch), dtype=torch.float32, device=cable.device)
+    if ncalls:
+        _lib.check(_lib.lib.d4w_beam_delays(dev.ptr(cable), nch, c0, fs, dev.ptr(p), ncalls, dev.out_ptr(k), dev.out_ptr(f), None,
+                                            dev.stream_ptr(cable)))
+    return k, f
+
+
+def beam_delays(cable_pos, c0, fs, pos, rounded=False):
+    """Travel times in samples from pos[c] = (x, y, z) to every channel, tau = |cable_pos[ch] - pos[c]| (1 / c0) fs in float64
+    (delay_table's expression).  pos: [ncalls x 3] or [3] (one call; the tables are still [1 x channel]).
+    rounded=False: (k int32, f float32), both [ncalls x channel], k = floor(tau) and f = float32(tau - k) with 0 <= f < 1 (a
+    fraction that rounds to 1.0f is carried into k): what beamform(order=1 or 3, delays=...) takes.
+    rounded=True: r int32 [ncalls x channel] = floor(tau + 0.5), delay_table's value at an arbitrary position (capped at 2^30, where
+    a NaN lands as well): what beamform(order=0, delays=...) takes.
+    The tables depend on the geometry, the rate and the positions only.  NumPy in -> NumPy out; a CUDA tensor in -> tensors on that
+    device and stream."""
+    _beam_geometry(cable_pos, c0, fs, pos)
+    c0, fs = float(c0), float(fs)
+    cable = _cable(cable_pos, _device_of(cable_pos, pos))
+    p = _positions(pos, cable.device)
+    as_tensor = any(dev.is_tensor(a) for a in (cable_pos, pos))
+    with torch.cuda.device(cable.device):
+        d = _beam_delays(cable, c0, fs, p, bool(rounded))
+    return _out(d, as_tensor) if rounded else (_out(d[0], as_tensor), _out(d[1], as_tensor))
+
+
+def _given_table(t, device):
+    t = t if dev.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+    return t.to(device).contiguous()
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+
+def _dtype_name(a):
+    return str(a.dtype).split(".")[-1] if hasattr(a, "dtype") else str(np.asarray(a).dtype)
+
+
+def _beam_geometry(cable_pos, c0, fs, pos):
+    """The checks beam_delays and beamform share, on the host before any device work: (channels, calls)."""
+    _pos_finite(c0=float(c0), fs=float(fs))
+    cs, ps = _shape(cable_pos), _shape(pos)
+    if len(cs) != 2 or cs[1] != 3 or cs[0] < 1:
+        raise ValueError("cable_pos must be [channel x 3], got %s" % (cs,))
+    if ps != (3,) and (len(ps) != 2 or ps[1] != 3):
+        raise ValueError("pos must be [x, y, z] or [ncalls x 3], got %s" % (ps,))
+    ncalls = 1 if len(ps) == 1 else ps[0]
+    if ncalls > beam_limits()[0]:
+        raise ValueError("%d calls are more than the %d one launch takes" % (ncalls, beam_limits()[0]))
+    return cs[0], ncalls
+
+
+def _beam_check(trace, fs, cable_pos, c0, pos, start, length, order, weights, next_block, delays):
+    """Every argument of beamform against the others, on the host before any device work:
+    (order, channels, samples, calls, length, the given delay tables as a tuple)."""
+    if isinstance(order, bool) or order not in (0, 1, 3):
+        raise ValueError("order must be 0, 1 or 3, got %r" % (order,))
+    order = int(order)
+    nch, ncalls = _beam_geometry(cable_pos, c0, fs, pos)
+    ts = _shape(trace)
+    if len(ts) != 2 or ts[0] < 1 or ts[1] < 1:
+        raise ValueError("trace must be a non-empty 2-D [channel x time] array, got %s" % (ts,))
+    if ts[0] != nch:
+        raise ValueError("trace has %d rows, cable_pos %d channels" % (ts[0], nch))
+    if next_block is not None:
+        bs = _shape(next_block)
+        if len(bs) != 2 or bs[1] < 1:
+            raise ValueError("next_block must be a non-empty 2-D [channel x time] array, got %s" % (bs,))
+        if bs[0] != nch:
+            raise ValueError("next_block has %d rows, trace %d" % (bs[0], nch))
+    nt = ts[1] if length is None else length
+    if isinstance(nt, bool) or nt != int(nt) or nt < 1:
+        raise ValueError("length must be a positive number of samples, got %r" % (length,))
+    nt = int(nt)
+    if nt > beam_limits()[1]:
+        raise ValueError("length %d is more than the %d one launch takes" % (nt, beam_limits()[1]))
+    ss = _shape(start)
+    if ss not in ((), (ncalls,)) or _dtype_name(start)[:3] not in ("int", "uin"):
+        raise ValueError("start must be an int or [ncalls] = (%d,) ints, got shape %s of %s" % (ncalls, ss, _dtype_name(start)))
+    if weights is not None and int(np.prod(_shape(weights))) != nch:
+        raise ValueError("weights must hold one value per channel (%d), got shape %s" % (nch, _shape(weights)))
+    tables = ()
+    if delays is not None:
+        tables = (delays,) if order == 0 else tuple(delays)
+        want = (("r", "int32"),) if order == 0 else (("k", "int32"), ("f", "float32"))
+        if len(tables) != len(want):
+            raise ValueError("delays must be (k, f) for order %d" % order)
+        for t, (name, dtype) in zip(tables, want):
+            if _shape(t) != (ncalls, nch) or _dtype_name(t) != dtype:
+                raise ValueError("delays: %s must be %s [ncalls x channel] = %s, got %s %s" % (name, dtype, (ncalls, nch), _dtype_name(t), _shape(t)))
+    return order, nch, ts[1], ncalls, nt, tables
+
+
+def _beam(e, pitch, nb, pitch_nb, kr, f, w, start, nt, order, normalize):
+    """The kernel on device tensors: beam [ncalls x nt] float32."""
+    import ctypes
+    nch, ns = e.shape
+    ncalls = kr.shape[0]
+    out = torch.empty((ncalls, nt), dtype=torch.float32, device=e.device)
+    nbytes = ctypes.c_size_t()
+    _lib.check(_lib.lib.d4w_beam_ws_bytes(nch, ncalls, nt, ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=e.device) if nbytes.value else None
+    _lib.check(_lib.lib.d4w_beamform_f32(dev.ptr(e), pitch, nch, ns, dev.ptr(nb) if nb is not None else None, pitch_nb,
+                                         nb.shape[1] if nb is not None else 0, dev.ptr(kr), dev.ptr(f) if f is not None else None,
+                                         dev.ptr(w) if w is not None else None, dev.ptr(start), ncalls, nt, order, int(bool(normalize)),
+                                         dev.out_ptr(out), dev.out_ptr(ws) if ws is not None else None, dev.stream_ptr(e)))
+    return out
+
+
+def beamform(trace, fs, cable_pos, c0, pos, start=0, length=None, order=1, weights=None, normalize=False, next_block=None, *, delays=None):
+    """Delay-and-sum beam of the strain toward located calls: the waveform of call c as the whole array hears it, every channel
+    advanced by its travel time from pos[c] = (x, y, z) and summed (about sqrt(channels) above the noise of one channel),
+        beam[c, j] = sum over ch, increasing, of weights[ch] v(ch, start[c] + j + delay[c, ch]),        0 <= j < length
+    Returns (beam [ncalls x length] float32, times [ncalls x length] float64 = (start[c] + j) / fs).
+
+    trace: [channel x time] strain; a CUDA float32 view with unit column stride is read in place (row pitch), anything else becomes
+    a float32 copy on the device.  pos: [ncalls x 3] or [3], e.g. the first three columns of solve_lq_batch's result.
+    start: the first emission sample, an int or [ncalls] ints, e.g. round(t0 fs); may be negative.  length: samples of the beam,
+    shared by the calls; default the samples of trace.
+    order: 0 = the nearest sample, v = x[ch, n + r], r = beam_delays(rounded=True) (one fmaf per term: a stack_grid term);
+    1 = linear, q = n + k, v = (1 - f) x[q] + f x[q + 1] with (k, f) = beam_delays(); 3 = four-point Lagrange on x[q - 1 .. q + 2].
+    A term contributes only if all of its taps lie inside the record; everything else adds nothing.
+    weights: float32 [channel], None = ones; a channel of weight 0 is not read at all (a NaN row under weight 0 changes nothing), a
+    NaN under a non-zero weight propagates.  normalize: divide every element by the sum of the weights of the channels that
+    contributed to it; an element without contributors is 0.
+    next_block: the next file of the same cable, [channel x ns2], same rules as trace: sample ns + i of a row is next_block[ch, i]
+    and the record is ns + ns2 long.  A call emitted in the last seconds of a file reaches the far channels in the next one; without
+    next_block those channels drop out of the beam.
+    delays: what beam_delays returns for this order (r for 0, (k, f) otherwise), built here when None.
+    float32 sums in increasing channel order in fixed segments of beam_limits()[2] channels, the segment partials added in
+    increasing order: run-to-run bit-identical, independent of the other calls of the batch and of a power-of-two scaling of trace.
+    NumPy in -> NumPy out; a CUDA tensor in -> tensors on that device and stream."""
+    order, nch, ns, ncalls, nt, tables = _beam_check(trace, fs, cable_pos, c0, pos, start, length, order, weights, next_block, delays)
+    c0, fs = float(c0), float(fs)
+    cable = _cable(cable_pos, _device_of(trace, cable_pos, pos, weights, next_block, start, *tables))
+    e, pitch = _env_block(trace, cable.device)
+    nb, pitch_nb = (None, 0) if next_block is None else _env_block(next_block, cable.device)
+    p = _positions(pos, cable.device)
+    if dev.is_tensor(start):
+        s = start.to(cable.device, torch.int64).reshape(-1)
+    else:
+        s = torch.from_numpy(np.array(start, dtype=np.int64).reshape(-1)).to(cable.device)
+    s = s.expand(ncalls).contiguous()
+    w = _weights(weights, nch, cable.device)
+    as_tensor = any(dev.is_tensor(a) for a in (trace, cable_pos, pos, weights, next_block, start) + tuple(tables))
+    with torch.cuda.device(cable.device):
+        if delays is None:
+            d = _beam_delays(cable, c0, fs, p, order == 0)
+            kr, f = (d, None) if order == 0 else d
+        else:
+            kr = _given_table(tables[0], cable.device)
+            f = _given_table(tables[1], cable.device) if order else None
+        if ncalls:
+            out = _beam(e, pitch, nb, pitch_nb, kr, f, w, s, nt, order, normalize)
+        else:
+            out = torch.empty((0, nt), dtype=torch.float32, device=cable.device)
+        # a tensor divisor: a true division (by a Python number torch multiplies with the reciprocal instead)
+        times = (s.to(torch.float64)[:, None] + torch.arange(nt, dtype=torch.float64, device=cable.device)[None, :]) \
+            / torch.full((), fs, dtype=torch.float64, device=cable.device)
+    return _out(out, as_tensor), _out(times, as_tensor)

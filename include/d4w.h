@@ -867,6 +867,51 @@ int d4w_stack_arrivals_f64(const float* env, int64_t pitch, int nch, int ns, dou
                            const double* pos, const double* t0, int ncalls, int halfwidth, double threshold,
                            const double* thresholds, const float* weights, double* Ti, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Delay-and-sum beam of the strain toward located calls (das4whales_amd/csrc/beam.hip; the reference has
+ * none of this): the waveform of a call with the array's gain.  Every pointer is DEVICE memory unless it returns a limit.
+ *
+ *   tau[c][ch] = |cable_pos[ch] - pos[c]| * (1 / c0) * fs      the stack's travel-time expression above, float64, 1 / c0
+ *     formed once on the host, no contraction; pos [ncalls][3].
+ *   r = (int) floor(tau + 0.5), capped at 2^30 (a NaN lands on the cap): d4w_stack_delays_i32's value at an arbitrary position.
+ *   k = (int) floor(tau), f = (float)(tau - k) in [0, 1); a fraction that rounds to 1.0f is carried into k; at the cap f = 0.
+ *   beam[c][j] = sum over ch, in increasing ch, of weights[ch] * v(ch, start[c] + j + delay[c][ch]),     0 <= j < length
+ *     order 0: delay = r, v = x[ch][n + r]                                  one fmaf(w, x, acc) per term, as d4w_stack_grid_f32
+ *     order 1: q = n + k, v = (1 - f) x[q] + f x[q + 1]
+ *     order 3: four-point Lagrange on x[q - 1 .. q + 2]: l(-1) = -f (f - 1) (f - 2) / 6, l(0) = (f + 1) (f - 1) (f - 2) / 2,
+ *              l(1) = -(f + 1) f (f - 2) / 2, l(2) = (f + 1) f (f - 1) / 6
+ *     over the channels with weights[ch] != 0 (a channel of weight 0 is not read at all) whose taps ALL lie inside the record
+ *     of ns + ns_next samples: sample ns + i of row ch is xnext[ch][i].  Everything else adds nothing.
+ *   x = [nch][pitch] float32, pitch in ELEMENTS (pitch >= ns: a column-sliced view is read in place); xnext = [nch][pitch_next]
+ *     or NULL (then ns_next = 0); weights [nch] float32 or NULL for ones; start [ncalls] int64, any sign.
+ *   The coefficients are formed in float32 and multiplied by the weight once per (call, channel); a term of order 1 or 3 is
+ *   the fmaf chain of its taps from the first product, added to the sum.  float32 sums by one thread per element and segment
+ *   of 128 consecutive channels, each segment from 0 in increasing channel order, the segment partials added in increasing
+ *   segment order, no atomics; with normalize the weight sums of the contributing channels take the same path and divide the
+ *   element (an element without contributors is 0).  The segment is a constant of the library: a beam is run-to-run
+ *   bit-identical, does not depend on the other calls of the batch, keeps its bits under a power-of-two scaling of x, and with
+ *   nch <= 128, order 0 and no normalize equals d4w_stack_grid_f32's column at that node bit for bit.
+ *
+ * d4w_beam_limits: the largest ncalls (65535) and length (2^30) of a call, and the segment (128).
+ * d4w_beam_tile: the consecutive samples one workgroup owns (what the tests size their shapes by).
+ * d4w_beam_delays: k, f [ncalls][nch] (both or neither) and / or r [ncalls][nch].
+ * d4w_beam_ws_bytes: the bytes of workspace d4w_beamform_f32 needs for that shape (0 with nch <= 128: ws may then be NULL).
+ * d4w_beamform_f32: beam [ncalls][length] float32.  k_or_r = r with order 0 (f is not read), k otherwise.
+ * Errors: D4W_EINVAL for a NULL required pointer, nch, ns, ncalls or length < 1, ncalls or length beyond the limits, more
+ *   than 65535 segments of channels,
+ *   pitch < ns, xnext with ns_next < 1 or pitch_next < ns_next, ns_next != 0 without xnext, fs or c0 not finite or <= 0,
+ *   an order other than 0, 1, 3, order 1 or 3 without f, k without f or f without k, neither (k, f) nor r, ws = NULL where
+ *   d4w_beam_ws_bytes is not 0.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_beam_limits(int* max_calls, int* max_length, int* segment);
+int d4w_beam_tile(int* samples);
+int d4w_beam_delays(const double* cable_pos, int nch, double c0, double fs, const double* pos, int ncalls, int32_t* k /* or NULL */,
+                    float* f /* or NULL */, int32_t* r /* or NULL */, void* stream);
+int d4w_beam_ws_bytes(int nch, int ncalls, int length, size_t* bytes);
+int d4w_beamform_f32(const float* x, int64_t pitch, int nch, int ns, const float* xnext /* or NULL */, int64_t pitch_next, int ns_next,
+                     const int32_t* k_or_r, const float* f /* NULL for order 0 */, const float* weights /* or NULL */,
+                     const int64_t* start, int ncalls, int length, int order, int normalize, float* beam, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
