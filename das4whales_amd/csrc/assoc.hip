@@ -2,7 +2,7 @@
 // hyperbolic moveouts |cable - node| / c0.  Beyond the reference, whose loc.solve_lq is fed hand-selected times.
 //
 //   pick k: channel ch_k, sample i_k, t_k = i_k / fs          node g = iy nx + ix at (xs[ix], ys[iy], z)   (misfit_grid's layout)
-//   e_kg = t_k - |cable[ch_k] - node_g| / c0                   bin(k, g) = floor((e_kg - lo) / dt)
+//   e_kg = t_k - |cable[ch_k] - node_g| / c0                   bin(k, g) = floor((e_kg - lo) / dt)       (the distance: moveout.h)
 //   votes[g][b] = #{k : bin(k, g) = b}, 0 <= b < nbins         s[g][b] = votes[g][b] + votes[g][b + 1], 0 <= b < nbins - 1
 //
 // One greedy round: the arg-max (g*, b*) of s (assoc_best), per channel the unassigned pick of bins b*, b* + 1 at g* nearest
@@ -42,7 +42,7 @@
 //
 // Cost model, in (pick, node) pair evaluations: initial vote K G ceil(nbins / 1024); per round at most nch G for the subtract,
 // (K / nch) nch = K for the select, and one read of the G nbins accumulator for the arg-max.
-#include "d4w_internal.h"
+#include "moveout.h"
 
 #ifndef D4W_EMU
 #pragma clang fp contract(off)
@@ -58,8 +58,7 @@ constexpr int kAssocParts = 1024;                // most partial results of the 
 
 // emission time of a pick at time t on the channel at (cx, cy, cz), heard from the node (px, py, pz)
 __device__ __forceinline__ double assoc_emit(double t, double cx, double cy, double cz, double px, double py, double pz, double inv_c0) {
-    const double dx = cx - px, dy = cy - py, dz = cz - pz;
-    return t - sqrt(dx * dx + dy * dy + dz * dz) * inv_c0;
+    return t - moveout_dist(cx, cy, cz, px, py, pz) * inv_c0;
 }
 // the bin of emission time e, -1 outside 0 .. nbins - 1 (and for a NaN)
 __device__ __forceinline__ int assoc_bin(double e, double lo, double inv_dt, int nbins) {
@@ -257,8 +256,6 @@ __global__ __launch_bounds__(kAssocThreads) void assoc_record(const int* __restr
     }
 }
 
-static bool assoc_pos(double v) { return std::isfinite(v) && v > 0.0; }
-
 // the checks the three entry points share; 0 or D4W_EINVAL with the message left behind
 static int assoc_check(const char* who, int npicks, int nch, int nx, int ny, int nbins, double fs, double c0, double dt, double lo, double z) {
     if (npicks < 0 || npicks > (1 << 30)) return fail(D4W_EINVAL, "%s: %d picks is not within 0 .. 2^30", who, npicks);
@@ -267,7 +264,7 @@ static int assoc_check(const char* who, int npicks, int nch, int nx, int ny, int
     if ((long long)nx * ny > INT32_MAX - kAssocNodes) return fail(D4W_EINVAL, "%s: the grid %d x %d has too many nodes", who, ny, nx);
     if (nbins < 2) return fail(D4W_EINVAL, "%s: %d bins, the pair score needs two", who, nbins);
     if (ceil_div(nbins, kAssocBins) > 65535) return fail(D4W_EINVAL, "%s: %d bins exceed the grid limit", who, nbins);
-    if (!assoc_pos(fs) || !assoc_pos(c0) || !assoc_pos(dt)) return fail(D4W_EINVAL, "%s: fs, c0 and dt must be positive and finite", who);
+    if (!positive_finite(fs) || !positive_finite(c0) || !positive_finite(dt)) return fail(D4W_EINVAL, "%s: fs, c0 and dt must be positive and finite", who);
     if (!std::isfinite(lo) || !std::isfinite(z)) return fail(D4W_EINVAL, "%s: lo and z must be finite", who);
     return D4W_OK;
 }

@@ -3,8 +3,8 @@
 // reference, which has nothing of the kind.  stack.hip sums envelopes along integer delays over a grid of nodes; this sums the
 // strain itself along fractional delays toward a few arbitrary positions and keeps the trace.
 //
-//   tau[c][ch] = |cable[ch] - pos[c]| (1 / c0) fs                          float64, stack_delay's expression, no contraction
-//   r = floor(tau + 0.5)   or   k = floor(tau), f = float32(tau - k) in [0, 1) (a fraction that rounds to 1.0f is carried)
+//   tau[c][ch] = |cable[ch] - pos[c]| (1 / c0) fs                          float64, moveout.h's moveout_samples
+//   r = floor(tau + 0.5)   or   k = floor(tau), f = float32(tau - k) in [0, 1)        moveout_round, moveout_split
 //   beam[c][j] = sum over ch, increasing, of w[ch] v(ch, start[c] + j + delay[c][ch]),           0 <= j < nt
 //     order 0: v = x[n + r]                       one fmaf(w, x, acc) per term: a stack_grid term
 //     order 1: q = n + k, v = (1 - f) x[q] + f x[q + 1]
@@ -20,7 +20,7 @@
 // from 0, and beam_reduce adds the segment partials in increasing segment order, the weight sums of normalize beside them.
 // The segment is a constant of the source, so an element has one defined sequence of roundings: run-to-run bit-identical,
 // independent of the other calls of the batch, exact under a power-of-two scaling of x, and with nch <= 128, order 0 and no
-// normalize the same bits as stack_grid's column at that node.
+// normalize the same bits as stack_grid's column at that node: r and stack.hip's table are the same two functions of moveout.h.
 //
 // beam_sum<ORDER, NORM>: grid (ceil(nt / 1024), segments, ncalls), 256 threads; a thread owns columns col0 + tid + 256 j,
 //   j < 4, lanes along consecutive samples: the reads are coalesced, unaligned.  The delay, the fraction and the weight of a
@@ -38,7 +38,7 @@
 //   2 ncalls nt ceil(nch / 128) words of partials written and read back (under 2 % of the reads).  Measured with segments
 //   of 256 / 128 / 64 channels at 11 020 x 12 000: one call of order 0 takes 0.60 / 0.38 / 0.30 ms (two, four or eight
 //   workgroups per compute unit), 64 calls 4.90 / 4.94 / 5.35 ms, and the workspace of 64 calls is 0.27 / 0.54 / 1.06 GB.
-#include "d4w_internal.h"
+#include "moveout.h"
 
 #ifndef D4W_EMU
 #pragma clang fp contract(off)
@@ -51,15 +51,8 @@ constexpr int kBeamCpt = 4;                                   // columns per thr
 constexpr int kBeamTile = kBeamThreads * kBeamCpt;            // columns per workgroup
 constexpr int kBeamSegment = 128;                             // channels one thread sums from 0
 constexpr int kBeamMaxCalls = 65535;                          // grid limit
-constexpr int kBeamMaxLength = 1 << 30;
-constexpr int kBeamDelayMax = 1 << 30;                        // stack.hip's cap
+constexpr int kBeamMaxLength = kMoveoutDelayMax;              // a beam is no longer than the longest delay
 constexpr long long kBeamStartMax = 1ll << 62;                // start is clamped here: the sums below cannot overflow
-
-// the travel time from (px, py, pz) to the channel at (cx, cy, cz) in samples: stack.hip's stack_delay before its floor
-__device__ __forceinline__ double beam_tau(double cx, double cy, double cz, double px, double py, double pz, double inv_c0, double fs) {
-    const double dx = cx - px, dy = cy - py, dz = cz - pz;
-    return sqrt(dx * dx + dy * dy + dz * dz) * inv_c0 * fs;
-}
 
 // grid (ceil(nch / 256), min(ncalls, 65535)); pos [ncalls][3]; k, f, r [ncalls][nch], each or NULL
 __global__ __launch_bounds__(kBeamThreads) void beam_delays(const double* __restrict__ cable, int nch, double inv_c0, double fs,
@@ -69,24 +62,13 @@ __global__ __launch_bounds__(kBeamThreads) void beam_delays(const double* __rest
     if (ch >= nch) return;
     const double cx = cable[3 * (size_t)ch], cy = cable[3 * (size_t)ch + 1], cz = cable[3 * (size_t)ch + 2];
     for (int c = blockIdx.y; c < ncalls; c += gridDim.y) {
-        const double tau = beam_tau(cx, cy, cz, pos[3 * (size_t)c], pos[3 * (size_t)c + 1], pos[3 * (size_t)c + 2], inv_c0, fs);
+        const double tau = moveout_samples(cx, cy, cz, pos[3 * (size_t)c], pos[3 * (size_t)c + 1], pos[3 * (size_t)c + 2], inv_c0, fs);
         const size_t e = (size_t)c * (size_t)nch + ch;
-        if (r) {
-            const double q = floor(tau + 0.5);
-            r[e] = q < (double)kBeamDelayMax ? (int)q : kBeamDelayMax;          // a NaN lands on the cap as well
-        }
+        if (r) r[e] = moveout_round(tau);
         if (k) {
-            const double q = floor(tau);
-            int kk = kBeamDelayMax;
-            float ff = 0.f;
-            if (q < (double)kBeamDelayMax) {
-                kk = (int)q;
-                ff = (float)(tau - q);
-                if (ff >= 1.0f) {                            // the fraction rounded up to 1: carried
-                    kk += 1;
-                    ff = 0.f;
-                }
-            }
+            int kk;
+            float ff;
+            moveout_split(tau, kk, ff);
             k[e] = kk;
             f[e] = ff;
         }
@@ -215,8 +197,6 @@ __global__ __launch_bounds__(kBeamThreads) void beam_reduce(const float* __restr
     }
 }
 
-static bool beam_pos(double v) { return std::isfinite(v) && v > 0.0; }
-
 static int beam_check_shape(const char* who, int nch, int ncalls, int length) {
     if (nch < 1 || nch > 65535 * kBeamSegment) return fail(D4W_EINVAL, "%s: %d channels, a launch takes 1 .. %d", who, nch, 65535 * kBeamSegment);
     if (ncalls < 1 || ncalls > kBeamMaxCalls) return fail(D4W_EINVAL, "%s: %d calls, a launch takes 1 .. %d", who, ncalls, kBeamMaxCalls);
@@ -279,7 +259,7 @@ int d4w_beam_delays(const double* cable_pos, int nch, double c0, double fs, cons
     if (!k && !r) return fail(D4W_EINVAL, "beam_delays: neither (k, f) nor r is asked for");
     if (nch < 1) return fail(D4W_EINVAL, "beam_delays: %d channels", nch);
     if (ncalls < 1 || ncalls > kBeamMaxCalls) return fail(D4W_EINVAL, "beam_delays: %d calls, a launch takes 1 .. %d", ncalls, kBeamMaxCalls);
-    if (!beam_pos(fs) || !beam_pos(c0)) return fail(D4W_EINVAL, "beam_delays: fs and c0 must be positive and finite");
+    if (!positive_finite(fs) || !positive_finite(c0)) return fail(D4W_EINVAL, "beam_delays: fs and c0 must be positive and finite");
     D4W_LAUNCH(beam_delays, dim3(ceil_div(nch, kBeamThreads), min(ncalls, 65535)), dim3(kBeamThreads), 0, stream, cable_pos, nch, 1.0 / c0, fs, pos,
                ncalls, (int*)k, f, (int*)r);
     return D4W_OK;
@@ -299,14 +279,13 @@ int d4w_beamform_f32(const float* x, int64_t pitch, int nch, int ns, const float
     if (!x || !k_or_r || !start || !beam) return fail(D4W_EINVAL, "bad argument");
     if (order != 0 && order != 1 && order != 3) return fail(D4W_EINVAL, "beamform: order %d is none of 0, 1, 3", order);
     if (order != 0 && !f) return fail(D4W_EINVAL, "beamform: order %d needs the fractions f", order);
-    const int rc = beam_check_shape("beamform", nch, ncalls, length);
+    int rc = beam_check_shape("beamform", nch, ncalls, length);
     if (rc) return rc;
-    if (ns < 1) return fail(D4W_EINVAL, "beamform: the block %d x %d is empty", nch, ns);
-    if (pitch < ns) return fail(D4W_EINVAL, "beamform: the row pitch %lld is below the %d samples of a row", (long long)pitch, ns);
+    rc = check_block("beamform", nch, ns, pitch);
+    if (rc) return rc;
     if (xnext) {
-        if (ns_next < 1) return fail(D4W_EINVAL, "beamform: the next block %d x %d is empty", nch, ns_next);
-        if (pitch_next < ns_next)
-            return fail(D4W_EINVAL, "beamform: the next block's row pitch %lld is below the %d samples of a row", (long long)pitch_next, ns_next);
+        rc = check_block("beamform, next block", nch, ns_next, pitch_next);
+        if (rc) return rc;
     } else if (ns_next != 0) {
         return fail(D4W_EINVAL, "beamform: %d samples of a next block that is not given", ns_next);
     }

@@ -7,8 +7,10 @@
 //
 // float64 throughout: positions are tens of kilometres and the answers matter at the millimetre and microsecond level.
 // Every output element is written by exactly one thread and every sum has a fixed order: run-to-run bit-identical, no atomics.
-// The compiler may not contract a * b + c in this file (pragma below): the travel time |cable - pos| / c0 is then the same
-// three roundings that NumPy makes, so noise-free arrival times leave residuals of exactly zero at the true position.  The
+// The compiler may not contract a * b + c in this file (pragma below, and moveout.h's own): the distance |cable - pos| is
+// moveout.h's moveout_dist, the one every localisation unit uses, and the division by c0 stays here as the reference's
+// "/ c0" (the other units multiply by a reciprocal; the two differ in the last bit).  The travel time is then the same
+// roundings that NumPy makes, so noise-free arrival times leave residuals of exactly zero at the true position.  The
 // accumulations that profit from a fused multiply-add ask for it by name.
 //
 // loc_solve<FIXZ>: ONE workgroup (256 threads, one compute unit) per call, the whole iteration inside the kernel.  Per
@@ -33,7 +35,7 @@
 //   an emission time of tens of seconds: t0 = K + mean, rms = sqrt(mean square - mean^2).  At a node where every e_j is the
 //   same the result is exactly rms = 0.
 // loc_arrival_times: one thread per (position, channel).
-#include "d4w_internal.h"
+#include "moveout.h"
 
 #ifndef D4W_EMU
 #pragma clang fp contract(off)
@@ -60,11 +62,13 @@ __device__ __forceinline__ double loc_wave_min(double v) {
     return v;
 }
 
-// the reference's row of G without the trailing 1, and R
-__device__ __forceinline__ void loc_row(double dx, double dy, double dz, double c0, double& g0, double& g1, double& g2, double& R) {
-    const double r2 = dx * dx + dy * dy;
+// the reference's row of G without the trailing 1, and R, for the position (nx, ny, nz) and the channel at (cx, cy, cz)
+__device__ __forceinline__ void loc_row(double nx, double ny, double nz, double cx, double cy, double cz, double c0, double& g0, double& g1,
+                                        double& g2, double& R) {
+    const double dx = nx - cx, dy = ny - cy, dz = nz - cz;
+    const double r2 = dx * dx + dy * dy;         // the first two terms of moveout_dist's sum
     const double adz = fabs(dz);
-    R = sqrt(r2 + dz * dz);
+    R = moveout_dist(nx, ny, nz, cx, cy, cz);
     if (r2 > 0.0) {
         const double inv = 1.0 / (R * c0);
         g0 = dx * inv;
@@ -164,7 +168,7 @@ __global__ __launch_bounds__(kLocThreads) void loc_solve(const double* __restric
             const double tt = t[ch];
             if (tt != tt) continue;
             double g[4], R;
-            loc_row(n0 - cable[3 * (size_t)ch], n1 - cable[3 * (size_t)ch + 1], n2 - cable[3 * (size_t)ch + 2], c0, g[0], g[1], g[2], R);
+            loc_row(n0, n1, n2, cable[3 * (size_t)ch], cable[3 * (size_t)ch + 1], cable[3 * (size_t)ch + 2], c0, g[0], g[1], g[2], R);
             if (FIXZ) g[2] = 1.0; else g[3] = 1.0;
             const double dt = tt - (n3 + R / c0);
             int q = 0;
@@ -262,8 +266,7 @@ __global__ __launch_bounds__(kLocThreads) void loc_misfit_grid(const double* __r
         for (int k = 0; k < m; ++k) {
             const double tt = sc[3 * kLocChunk + k];
             if (tt != tt) continue;              // the same for every thread of the workgroup
-            const double dx = sc[k] - px, dy = sc[kLocChunk + k] - py, dz = sc[2 * kLocChunk + k] - z;
-            double e = tt - sqrt(dx * dx + dy * dy + dz * dz) / c0;
+            double e = tt - moveout_dist(sc[k], sc[kLocChunk + k], sc[2 * kLocChunk + k], px, py, z) / c0;
             if (cnt == 0) K = e;
             e -= K;
             s1 += e;
@@ -291,12 +294,10 @@ __global__ __launch_bounds__(kLocThreads) void loc_arrival_times(const double* _
     const int ch = blockIdx.x * kLocThreads + threadIdx.x;
     if (ch >= nch) return;
     const size_t p = blockIdx.y;
-    const double dx = cable[3 * (size_t)ch] - pos[3 * p], dy = cable[3 * (size_t)ch + 1] - pos[3 * p + 1],
-                 dz = cable[3 * (size_t)ch + 2] - pos[3 * p + 2];
-    out[p * (size_t)nch + ch] = t0[p] + sqrt(dx * dx + dy * dy + dz * dz) / c0;
+    const double d = moveout_dist(cable[3 * (size_t)ch], cable[3 * (size_t)ch + 1], cable[3 * (size_t)ch + 2], pos[3 * p], pos[3 * p + 1],
+                                  pos[3 * p + 2]);
+    out[p * (size_t)nch + ch] = t0[p] + d / c0;
 }
-
-static bool loc_c0_ok(double c0) { return std::isfinite(c0) && c0 > 0.0; }
 
 }  // namespace d4w
 
@@ -310,7 +311,7 @@ int d4w_loc_solve_f64(const double* cable_pos, int nch, const double* Ti, int nc
     if (!cable_pos || !Ti || !n_out || !gtg || !ssr || !npick) return fail(D4W_EINVAL, "bad argument");
     if (nch < 1) return fail(D4W_EINVAL, "loc_solve: %d channels", nch);
     if (ncalls < 0) return fail(D4W_EINVAL, "loc_solve: %d calls", ncalls);
-    if (!loc_c0_ok(c0)) return fail(D4W_EINVAL, "loc_solve: the speed of sound must be positive and finite");
+    if (!positive_finite(c0)) return fail(D4W_EINVAL, "loc_solve: the speed of sound must be positive and finite");
     if (nbiter < 0 || nbiter > 100000) return fail(D4W_EINVAL, "loc_solve: Nbiter = %d is not within 0 .. 100000", nbiter);
     if (nbiter > 0 && !history) return fail(D4W_EINVAL, "loc_solve: the history of %d iterations needs its output", nbiter);
     if (ncalls == 0) return D4W_OK;
@@ -330,7 +331,7 @@ int d4w_loc_misfit_grid_f64(const double* cable_pos, int nch, const double* Ti, 
     if (ncalls < 0 || ncalls > 65535) return fail(D4W_EINVAL, "loc_misfit_grid: %d calls is not within 0 .. 65535", ncalls);
     if (nx < 1 || ny < 1) return fail(D4W_EINVAL, "loc_misfit_grid: the grid %d x %d is empty", ny, nx);
     if (ceil_div(ny, kLocTileH) > 65535) return fail(D4W_EINVAL, "loc_misfit_grid: %d grid rows exceed the grid limit", ny);
-    if (!loc_c0_ok(c0)) return fail(D4W_EINVAL, "loc_misfit_grid: the speed of sound must be positive and finite");
+    if (!positive_finite(c0)) return fail(D4W_EINVAL, "loc_misfit_grid: the speed of sound must be positive and finite");
     if (!std::isfinite(z)) return fail(D4W_EINVAL, "loc_misfit_grid: z must be finite");
     if (ncalls == 0) return D4W_OK;
     const dim3 grid(ceil_div(nx, kLocTileW), ceil_div(ny, kLocTileH), ncalls);
@@ -343,7 +344,7 @@ int d4w_loc_arrival_times_f64(const double* cable_pos, int nch, const double* po
     if (!cable_pos || !pos || !t0 || !out) return fail(D4W_EINVAL, "bad argument");
     if (nch < 1) return fail(D4W_EINVAL, "loc_arrival_times: %d channels", nch);
     if (npos < 0 || npos > 65535) return fail(D4W_EINVAL, "loc_arrival_times: %d positions is not within 0 .. 65535", npos);
-    if (!loc_c0_ok(c0)) return fail(D4W_EINVAL, "loc_arrival_times: the speed of sound must be positive and finite");
+    if (!positive_finite(c0)) return fail(D4W_EINVAL, "loc_arrival_times: the speed of sound must be positive and finite");
     if (npos == 0) return D4W_OK;
     D4W_LAUNCH(loc_arrival_times, dim3(ceil_div(nch, kLocThreads), npos), dim3(kLocThreads), 0, stream, cable_pos, nch, pos, t0, c0,
                out);

@@ -7,11 +7,12 @@
 //   stack[g][k - k0] = sum over ch, in increasing ch, of w[ch] env[ch][k + d[g][ch]]
 //                      over the channels with w[ch] != 0 and 0 <= k + d[g][ch] < ns,        k0 <= k < k1
 //
-// Arithmetic.  The delay is float64 with assoc_emit's difference and square-root expression, the reciprocal of c0 formed once
-// on the host, and no contraction (pragma below): stack_delay is inlined into the table kernel and into the arrivals kernel,
-// and only without contraction is it the same sequence of roundings in both.  The sum is float32, one fmaf per term, in
-// increasing channel order, by one thread per element: no atomics, no split over channels, so every element has one defined
-// sequence of roundings, is run-to-run bit-identical, and is the same in both forms of the kernel.
+// Arithmetic.  The delay is moveout.h's: float64, the distance every localisation unit shares, the reciprocal of c0 formed once
+// on the host, and no contraction (the header sets it for its own functions): stack_delay is inlined into the table kernel
+// and into the arrivals kernel, and beam.hip makes the same two calls, the same sequence of roundings in all three.  The sum
+// is float32, one fmaf per term, in increasing channel order, by one thread per element: no atomics, no split over channels,
+// so every element has one defined sequence of roundings, is run-to-run bit-identical, and is the same in both forms of the
+// kernel.
 //
 // stack_grid<WINDOW, NORM>: grid (ceil(nt / 1024), tiles); with normalize ceil(nt / 512).  A workgroup of 256 threads owns a
 //   tile of 4 x 4 neighbouring nodes (in ix and iy: neighbours in space have neighbouring delays, a run of flat indices would
@@ -37,7 +38,7 @@
 // Cost model, in (node, channel, column) triples: the window form spends one LDS word read and one fma per triple plus
 //   (1024 + spread) / (16 x 1024) global words; the direct form one global word read and ~5 vector instructions per triple.
 //   ds_read_b32 delivers 32 words per clock and compute unit against 128 fma: the model's limit is the LDS read rate.
-#include "d4w_internal.h"
+#include "moveout.h"
 
 #include <type_traits>
 
@@ -58,14 +59,11 @@ constexpr int kStackSpread = 992;                            // largest dmax - d
 constexpr int stack_cpt(bool norm) { return norm ? 2 : 4; }
 constexpr int stack_cols(bool norm) { return kStackThreads * stack_cpt(norm); }
 constexpr int stack_span(bool norm) { return stack_cols(norm) + kStackSpread + kStackAlign; }
-constexpr int kStackDelayMax = 1 << 30;
 constexpr int kBestCols = 64, kBestGroups = kStackThreads / kBestCols;
 
-// the travel time from (px, py, pz) to the channel at (cx, cy, cz) in samples, rounded half up; the only form of it here
+// the travel time from (px, py, pz) to the channel at (cx, cy, cz) in samples, rounded half up (moveout.h)
 __device__ __forceinline__ int stack_delay(double cx, double cy, double cz, double px, double py, double pz, double inv_c0, double fs) {
-    const double dx = cx - px, dy = cy - py, dz = cz - pz;
-    const double q = floor(sqrt(dx * dx + dy * dy + dz * dz) * inv_c0 * fs + 0.5);
-    return q < (double)kStackDelayMax ? (int)q : kStackDelayMax;         // a NaN lands on the cap as well
+    return moveout_round(moveout_samples(cx, cy, cz, px, py, pz, inv_c0, fs));
 }
 
 __device__ __forceinline__ int stack_wrap_add(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
@@ -332,19 +330,11 @@ __global__ __launch_bounds__(kStackThreads) void stack_arrivals(const float* __r
     }
 }
 
-static bool stack_pos(double v) { return std::isfinite(v) && v > 0.0; }
-
 static int stack_check_grid(const char* who, int nx, int ny) {
     if (nx < 1 || ny < 1) return fail(D4W_EINVAL, "%s: the grid %d x %d is empty", who, ny, nx);
     if ((long long)nx * ny > (long long)INT32_MAX / 2) return fail(D4W_EINVAL, "%s: the grid %d x %d has too many nodes", who, ny, nx);
     if ((long long)ceil_div(nx, kStackTX) * ceil_div(ny, kStackTY) > 65535)
         return fail(D4W_EINVAL, "%s: the grid %d x %d has more than 65535 tiles of %d x %d nodes", who, ny, nx, kStackTY, kStackTX);
-    return D4W_OK;
-}
-
-static int stack_check_env(const char* who, int nch, int ns, long long pitch) {
-    if (nch < 1 || ns < 1) return fail(D4W_EINVAL, "%s: the block %d x %d is empty", who, nch, ns);
-    if (pitch < ns) return fail(D4W_EINVAL, "%s: the row pitch %lld is below the %d samples of a row", who, pitch, ns);
     return D4W_OK;
 }
 
@@ -373,7 +363,7 @@ int d4w_stack_delays_i32(const double* cable_pos, int nch, double c0, double fs,
     if (nch < 1) return fail(D4W_EINVAL, "stack_delays: %d channels", nch);
     const int rc = stack_check_grid("stack_delays", nx, ny);
     if (rc) return rc;
-    if (!stack_pos(fs) || !stack_pos(c0)) return fail(D4W_EINVAL, "stack_delays: fs and c0 must be positive and finite");
+    if (!positive_finite(fs) || !positive_finite(c0)) return fail(D4W_EINVAL, "stack_delays: fs and c0 must be positive and finite");
     if (!std::isfinite(z)) return fail(D4W_EINVAL, "stack_delays: z must be finite");
     const int ngrid = nx * ny;
     D4W_LAUNCH(stack_delays, dim3(ceil_div(nch, kStackThreads), min(ngrid, 65535)), dim3(kStackThreads), 0, stream, cable_pos, nch, 1.0 / c0, fs,
@@ -384,14 +374,14 @@ int d4w_stack_delays_i32(const double* cable_pos, int nch, double c0, double fs,
 int d4w_stack_grid_f32(const float* env, int64_t pitch, int nch, int ns, const int32_t* delays, const float* weights, int nx, int ny, int k0,
                        int k1, int normalize, int form, float* stack, int32_t* info, void* stream) {
     if (!env || !delays || !stack) return fail(D4W_EINVAL, "bad argument");
-    int rc = stack_check_env("stack_grid", nch, ns, pitch);
+    int rc = check_block("stack_grid", nch, ns, pitch);
     if (rc) return rc;
     rc = stack_check_grid("stack_grid", nx, ny);
     if (rc) return rc;
     if (form < 0 || form > 2) return fail(D4W_EINVAL, "stack_grid: form %d is none of 0 (choose), 1 (window), 2 (direct)", form);
     if (form != 2 && !info) return fail(D4W_EINVAL, "stack_grid: form %d decides on the device and needs info", form);
     if (k0 >= k1) return fail(D4W_EINVAL, "stack_grid: the column range [%d, %d) is empty", k0, k1);
-    if (k0 < -kStackDelayMax || k1 > kStackDelayMax) return fail(D4W_EINVAL, "stack_grid: the column range [%d, %d) leaves +-2^30", k0, k1);
+    if (k0 < -kMoveoutDelayMax || k1 > kMoveoutDelayMax) return fail(D4W_EINVAL, "stack_grid: the column range [%d, %d) leaves +-2^30", k0, k1);
     if ((long long)k1 - (long long)k0 > (long long)INT32_MAX) return fail(D4W_EINVAL, "stack_grid: the column range [%d, %d) holds more than 2^31 - 1 columns", k0, k1);
     const int nt = k1 - k0;
     if (info) D4W_HIP(hipMemsetAsync(info, 0, 2 * sizeof(int32_t), (hipStream_t)stream));
@@ -416,11 +406,11 @@ int d4w_stack_arrivals_f64(const float* env, int64_t pitch, int nch, int ns, dou
                            const double* t0, int ncalls, int halfwidth, double threshold, const double* thresholds, const float* weights,
                            double* Ti, void* stream) {
     if (!env || !cable_pos || !pos || !t0 || !Ti) return fail(D4W_EINVAL, "bad argument");
-    const int rc = stack_check_env("stack_arrivals", nch, ns, pitch);
+    const int rc = check_block("stack_arrivals", nch, ns, pitch);
     if (rc) return rc;
     if (ncalls < 1) return fail(D4W_EINVAL, "stack_arrivals: %d calls", ncalls);
     if (halfwidth < 0) return fail(D4W_EINVAL, "stack_arrivals: the half-width %d is negative", halfwidth);
-    if (!stack_pos(fs) || !stack_pos(c0)) return fail(D4W_EINVAL, "stack_arrivals: fs and c0 must be positive and finite");
+    if (!positive_finite(fs) || !positive_finite(c0)) return fail(D4W_EINVAL, "stack_arrivals: fs and c0 must be positive and finite");
     D4W_LAUNCH(stack_arrivals, dim3(ceil_div(nch, kStackWaves), min(ncalls, 65535)), dim3(kStackThreads), 0, stream, env, (long long)pitch, nch,
                ns, fs, cable_pos, 1.0 / c0, pos, t0, ncalls, halfwidth, threshold, thresholds, weights, Ti);
     return D4W_OK;

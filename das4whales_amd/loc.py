@@ -13,7 +13,9 @@ index arithmetic of the other namespaces; for tensors they stay on the device.
 Arrival times that are NaN mean "no pick on this channel": the solver and the grid skip them (the reference has no such
 notion -- its np.min(Ti) turns the whole result into NaN).
 """
+import ctypes
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -42,12 +44,19 @@ def _f64(x, device=None):
     return torch.from_numpy(a).to(device or ("cuda:%d" % torch.cuda.current_device()))
 
 
+# Two rules for the container of a result, different on purpose.  _back serves the functions that mirror the reference: a host
+# tensor in gives a host tensor back.  _out serves the later families (vote, stack, beam): any tensor in, on the host or on a
+# device, gives a tensor on the device the work ran on, and only NumPy in gives NumPy back.
 def _back(y, *templates):
     """The device result in the callers' container: a tensor where any input was one (on the host if none was on a device)."""
     ts = [t for t in templates if dev.is_tensor(t)]
     if ts:
         return y if any(t.is_cuda for t in ts) else y.cpu()
     return y.cpu().numpy()
+
+
+def _out(y, as_tensor):
+    return y if as_tensor else y.cpu().numpy()
 
 
 def _device_of(*xs):
@@ -57,11 +66,115 @@ def _device_of(*xs):
     return None
 
 
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+
+def _count(a):
+    return int(np.prod(_shape(a)))
+
+
+def _dtype_name(a):
+    return str(a.dtype).split(".")[-1] if hasattr(a, "dtype") else str(np.asarray(a).dtype)
+
+
+def _pos_finite(**kw):
+    for name, v in kw.items():
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError("%s must be positive and finite, got %r" % (name, v))
+
+
+def _channels(cable_pos):
+    """The one shape check of cable_pos, on the host: the number of channels."""
+    cs = _shape(cable_pos)
+    if len(cs) != 2 or cs[1] != 3 or cs[0] < 1:
+        raise ValueError("cable_pos must be [channel x 3], got %s" % (cs,))
+    return cs[0]
+
+
 def _cable(cable_pos, device):
-    c = _f64(cable_pos, device)
-    if c.dim() != 2 or c.shape[1] != 3 or c.shape[0] < 1:
-        raise ValueError("cable_pos must be [channel x 3], got %s" % (tuple(c.shape),))
-    return c
+    _channels(cable_pos)
+    return _f64(cable_pos, device)
+
+
+_SKIP = object()                       # an argument a function does not have (None may be a caller's value)
+
+
+def _npos(pos, t0=_SKIP):
+    """The one check of positions, on the host: pos is [x, y, z] or [n x 3], t0 a scalar or [n].  Returns n."""
+    ps = _shape(pos)
+    if ps != (3,) and (len(ps) != 2 or ps[1] != 3):
+        raise ValueError("pos must be [x, y, z] or [n x 3], got %s" % (ps,))
+    n = 1 if len(ps) == 1 else ps[0]
+    if t0 is not _SKIP and _count(t0) not in (1, n):
+        raise ValueError("t0 must be a scalar or one value per position (%d), got shape %s" % (n, _shape(t0)))
+    return n
+
+
+def _positions(pos, t0, device):
+    """pos and t0 after _npos on the device: (p [n x 3], t [n] or None)."""
+    p = _f64(pos, device)
+    p = p.reshape(1, 3) if p.dim() == 1 else p
+    return p, (None if t0 is _SKIP else _f64(t0, device).reshape(-1).expand(p.shape[0]).contiguous())
+
+
+def _env_block(env, device):
+    """(float32 CUDA tensor [nch x ns] with unit column stride, row pitch in elements).  A column-sliced float32 CUDA view is
+    taken as it is; everything else becomes a contiguous float32 copy on the device."""
+    if (dev.is_tensor(env) and env.is_cuda and env.dtype == torch.float32 and env.device == torch.device(device)
+            and env.stride(1) == 1 and (env.stride(0) >= env.shape[1] or env.shape[0] == 1)):
+        return env, (env.stride(0) if env.shape[0] > 1 else env.shape[1])
+    e = dev.to_device_f32(env, device)
+    return e, e.shape[1]
+
+
+def _check(cable_pos, c0, fs, *, block=_SKIP, name="env", next_block=None, weights=None, xs=_SKIP, ys=_SKIP, pos=_SKIP, t0=_SKIP):
+    """The arguments the vote, the stack and the beam share, checked against each other on the host: a bad call raises
+    ValueError before any device work, with or without a GPU.  Returns the object _upload completes, so far with c0, fs and the
+    sizes nch, ns (block), nx, ny (grid axes) and ncalls (positions); a function's own checks go between the two."""
+    a = SimpleNamespace(c0=float(c0), fs=float(fs), nch=_channels(cable_pos))
+    _pos_finite(c0=a.c0, fs=a.fs)
+    for what, b in ((name, block), ("next_block", next_block)):
+        if b is _SKIP or b is None:
+            continue
+        if getattr(b, "ndim", 0) != 2 or b.shape[0] < 1 or b.shape[1] < 1:
+            raise ValueError("%s must be a non-empty 2-D [channel x time] array, got shape %s" % (what, _shape(b)))
+        if b.shape[0] != a.nch:
+            raise ValueError("%s has %d rows, cable_pos %d channels" % (what, b.shape[0], a.nch))
+    if block is not _SKIP:
+        a.ns = block.shape[1]
+    if weights is not None and _count(weights) != a.nch:
+        raise ValueError("weights must hold one value per channel (%d), got shape %s" % (a.nch, _shape(weights)))
+    if xs is not _SKIP:
+        a.nx, a.ny = _count(xs), _count(ys)
+        if a.nx < 1 or a.ny < 1:
+            raise ValueError("the grid needs at least one node")
+    if pos is not _SKIP:
+        a.ncalls = _npos(pos, t0)
+    a.given = (block, cable_pos, xs, ys, pos, t0, weights, next_block)
+    return a
+
+
+def _upload(a, like=(), device=None):
+    """The arguments of _check on one device: cable [nch x 3], e and pitch (the block; nb and pitch_nb the next one), w [nch] or
+    None, gx and gy, p [ncalls x 3] and t [ncalls] or None, each where it was given.  The device is `device`, or that of the
+    first CUDA tensor among the arguments and `like`, or the current one; as_tensor says whether any of them is a tensor."""
+    block, cable_pos, xs, ys, pos, t0, weights, next_block = given = a.given
+    del a.given
+    a.as_tensor = any(dev.is_tensor(x) for x in given + tuple(like))
+    a.cable = _f64(cable_pos, device if device is not None else _device_of(*(given + tuple(like))))
+    d = a.device = a.cable.device
+    if block is not _SKIP:
+        a.e, a.pitch = _env_block(block, d)
+    a.nb, a.pitch_nb = (None, 0) if next_block is None else _env_block(next_block, d)
+    a.w = None
+    if weights is not None:
+        a.w = dev.to_device_f32(weights if dev.is_tensor(weights) else np.asarray(weights).reshape(1, -1), d).reshape(-1)
+    if xs is not _SKIP:
+        a.gx, a.gy = _f64(xs, d).reshape(-1), _f64(ys, d).reshape(-1)
+    if pos is not _SKIP:
+        a.p, a.t = _positions(pos, t0, d)
+    return a
 
 
 def _calls(Ti, nch, device):
@@ -130,19 +243,9 @@ def _covariance(gtg, var, quiet=False):
 def calc_arrival_times(t0, cable_pos, pos, c0):
     """Theoretical arrival times of a call emitted at `t0` from `pos` = [x, y, z] at every channel (loc.py:13-25).  Beyond the
     reference: `pos` = [npos x 3] with `t0` a scalar or [npos] gives [npos x channel] in one launch."""
-    device = _device_of(cable_pos, pos, t0)
-    cable = _cable(cable_pos, device)
-    p = _f64(pos, cable.device)
-    single = p.dim() == 1
-    p = p.reshape(1, -1) if single else p
-    if p.dim() != 2 or p.shape[1] != 3:
-        raise ValueError("pos must be [x, y, z] or [npos x 3], got %s" % (tuple(p.shape),))
-    npos, nch = p.shape[0], cable.shape[0]
-    t = _f64(t0, cable.device).reshape(-1)
-    if t.numel() == 1:
-        t = t.expand(npos).contiguous()
-    if t.numel() != npos:
-        raise ValueError("t0 must be a scalar or one value per position")
+    nch, npos, single = _channels(cable_pos), _npos(pos, t0), len(_shape(pos)) == 1
+    cable = _f64(cable_pos, _device_of(cable_pos, pos, t0))
+    p, t = _positions(pos, t0, cable.device)
     out = torch.empty((npos, nch), dtype=torch.float64, device=cable.device)
     with torch.cuda.device(cable.device):
         for a in range(0, npos, _MAX_GRID_Z):
@@ -312,10 +415,10 @@ def first_guess_grid(Ti, cable_pos, c0, xs, ys, z):
 # ------------------------------------------------------------------------------------------
 # beyond the reference: association of picks into calls (csrc/assoc.hip)
 # ------------------------------------------------------------------------------------------
-def _pick_table(picks, nch, device):
-    """The picks as (packed [2 x K] int64 on the device ordered by (channel, sample), counts [nch] int32 on the device,
-    order, device output?).  order: None, or the positions in the caller's table of the rows of `packed`.  A PickRows
-    stays on the device; every other form is a small host table, checked and sorted there."""
+def _pick_table(picks, nch):
+    """The picks as an object of packed [2 x K] int64 ordered by (channel, sample), counts [nch] int32, order (None, or the
+    positions in the caller's table of the rows of `packed`) and on_device (a device form came in).  A PickRows stays on the
+    device; every other form is a small host table, checked and sorted here and still on the host."""
     from .detect import PickRows, convert_pick_times
     if isinstance(picks, PickRows):
         packed, counts = picks.packed, picks.counts.to(torch.int32)
@@ -323,7 +426,7 @@ def _pick_table(picks, nch, device):
             raise ValueError("the picks cover %d channels, cable_pos has %d" % (counts.numel(), nch))
         if counts.numel() < nch:
             counts = torch.cat([counts, counts.new_zeros(nch - counts.numel())])
-        return packed.contiguous(), counts.contiguous(), None, True
+        return SimpleNamespace(packed=packed.contiguous(), counts=counts.contiguous(), order=None, on_device=True)
     on_device = dev.is_tensor(picks) or (isinstance(picks, tuple) and any(dev.is_tensor(p) for p in picks))
     if isinstance(picks, tuple) and len(picks) == 2:                      # what select_picked_times returns
         picks = [p.cpu().numpy() if dev.is_tensor(p) else np.asarray(p) for p in picks]
@@ -350,16 +453,15 @@ def _pick_table(picks, nch, device):
         order = np.lexsort((tab[1], tab[0]))                               # stable: equal picks keep the caller's order
         tab = tab[:, order]
     counts = np.bincount(tab[0], minlength=nch).astype(np.int32)
-    d = device or ("cuda:%d" % torch.cuda.current_device())
-    return (torch.from_numpy(np.ascontiguousarray(tab)).to(d), torch.from_numpy(counts).to(d), order, on_device)
+    return SimpleNamespace(packed=torch.from_numpy(np.ascontiguousarray(tab)), counts=torch.from_numpy(counts), order=order,
+                           on_device=on_device)
 
 
 def _assoc_range(packed, fs, cable, c0, gx, gy, z, dt, t0_range):
-    """(lo, nbins, edges as float64 ndarray).  The default range reads the table's extreme samples and the small arrays on the
-    host: lo = min t - Dmax / c0, hi = max t, Dmax = the largest distance between the 8 corners of the cable's bounding box
-    and the 4 corners of the grid rectangle at depth z.  Without picks the default takes min t = max t = 0."""
-    if not (np.isfinite(dt) and dt > 0 and np.isfinite(fs) and fs > 0 and np.isfinite(c0) and c0 > 0):
-        raise ValueError("dt, fs and c0 must be positive and finite")
+    """The bin range as an object of lo, nbins and edges (float64 ndarray).  The default range reads the table's extreme samples
+    and the small arrays on the host: lo = min t - Dmax / c0, hi = max t, Dmax = the largest distance between the 8 corners of
+    the cable's bounding box and the 4 corners of the grid rectangle at depth z.  Without picks the default takes
+    min t = max t = 0."""
     if t0_range is not None:
         lo, hi = (float(v) for v in t0_range)
     else:
@@ -381,20 +483,19 @@ def _assoc_range(packed, fs, cable, c0, gx, gy, z, dt, t0_range):
     nbins = int(np.ceil((hi - lo) / dt)) + 1
     if nbins < 2:
         raise ValueError("the emission-time range [%g, %g] gives %d bin of %g s; the pair score needs two" % (lo, hi, nbins, dt))
-    return lo, nbins, lo + dt * np.arange(nbins + 1)
+    return SimpleNamespace(lo=lo, nbins=nbins, edges=lo + dt * np.arange(nbins + 1))
 
 
 def _assoc_setup(picks, fs, cable_pos, c0, xs, ys, z, dt, t0_range):
-    device = picks.counts.device if hasattr(picks, "counts") else _device_of(picks, cable_pos, xs, ys)
-    cable = _cable(cable_pos, device)
-    gx, gy = _f64(xs, cable.device).reshape(-1), _f64(ys, cable.device).reshape(-1)
-    if gx.numel() < 1 or gy.numel() < 1:
-        raise ValueError("the grid needs at least one node")
-    fs, c0, z, dt = float(fs), float(c0), float(z), float(dt)
-    packed, counts, order, on_device = _pick_table(picks, cable.shape[0], cable.device)
-    lo, nbins, edges = _assoc_range(packed, fs, cable, c0, gx, gy, z, dt, t0_range)
-    as_tensor = on_device or any(dev.is_tensor(a) for a in (cable_pos, xs, ys))
-    return cable, gx, gy, fs, c0, z, dt, packed, counts, order, lo, nbins, edges, as_tensor
+    """(the shared arguments with z and dt, the pick table on their device, the bin range)."""
+    a = _check(cable_pos, c0, fs, xs=xs, ys=ys)
+    a.z, a.dt = float(z), float(dt)
+    _pos_finite(dt=a.dt)
+    t = _pick_table(picks, a.nch)
+    _upload(a, device=t.counts.device if t.counts.is_cuda else _device_of(picks))
+    a.as_tensor = a.as_tensor or t.on_device
+    t.packed, t.counts = t.packed.to(a.device), t.counts.to(a.device)
+    return a, t, _assoc_range(t.packed, a.fs, a.cable, a.c0, a.gx, a.gy, a.z, a.dt, t0_range)
 
 
 def _vote(packed, idx, sign, accumulate, cable, fs, c0, gx, gy, z, lo, dt, nbins, votes, stop):
@@ -403,10 +504,6 @@ def _vote(packed, idx, sign, accumulate, cable, fs, c0, gx, gy, z, lo, dt, nbins
                                            idx.numel() if idx is not None else 0, sign, accumulate, dev.ptr(cable), cable.shape[0],
                                            fs, c0, dev.ptr(gx), gx.numel(), dev.ptr(gy), gy.numel(), z, lo, dt, nbins,
                                            dev.out_ptr(votes), dev.ptr(stop) if stop is not None else None, dev.stream_ptr(cable)))
-
-
-def _out(y, as_tensor):
-    return y if as_tensor else y.cpu().numpy()
 
 
 def vote_grid(picks, fs, cable_pos, c0, xs, ys, z, dt, t0_range=None):
@@ -420,12 +517,11 @@ def vote_grid(picks, fs, cable_pos, c0, xs, ys, z, dt, t0_range=None):
     the emission times covered; None: lo = earliest pick - Dmax / c0, hi = latest pick, Dmax the largest distance between
     the corners of the cable's bounding box and of the grid.  nbins = ceil((hi - lo) / dt) + 1.  Picks whose bin falls
     outside are not counted.  NumPy in -> NumPy out; a CUDA tensor or PickRows in -> tensors on that device."""
-    cable, gx, gy, fs, c0, z, dt, packed, counts, order, lo, nbins, edges, as_tensor = _assoc_setup(picks, fs, cable_pos, c0, xs, ys, z,
-                                                                                                  dt, t0_range)
-    with torch.cuda.device(cable.device):
-        votes = torch.empty((gy.numel(), gx.numel(), nbins), dtype=torch.int32, device=cable.device)
-        _vote(packed, None, 1, 0, cable, fs, c0, gx, gy, z, lo, dt, nbins, votes, None)
-    return _out(votes, as_tensor), (torch.from_numpy(edges).to(cable.device) if as_tensor else edges)
+    a, t, r = _assoc_setup(picks, fs, cable_pos, c0, xs, ys, z, dt, t0_range)
+    with torch.cuda.device(a.device):
+        votes = torch.empty((a.ny, a.nx, r.nbins), dtype=torch.int32, device=a.device)
+        _vote(t.packed, None, 1, 0, a.cable, a.fs, a.c0, a.gx, a.gy, a.z, r.lo, a.dt, r.nbins, votes, None)
+    return _out(votes, a.as_tensor), (torch.from_numpy(r.edges).to(a.device) if a.as_tensor else r.edges)
 
 
 def associate_picks(picks, fs, cable_pos, c0, xs, ys, z, dt, min_picks, max_calls=64, t0_range=None, return_votes=False):
@@ -449,13 +545,11 @@ def associate_picks(picks, fs, cable_pos, c0, xs, ys, z, dt, min_picks, max_call
     if int(max_calls) < 0:
         raise ValueError("max_calls must not be negative")
     min_picks, max_calls = int(min_picks), int(max_calls)
-    cable, gx, gy, fs, c0, z, dt, packed, counts, order, lo, nbins, edges, as_tensor = _assoc_setup(picks, fs, cable_pos, c0, xs, ys, z,
-                                                                                                  dt, t0_range)
-    d, nch, K = cable.device, cable.shape[0], packed.shape[1]
-    nx, ny = gx.numel(), gy.numel()
+    a, t, r = _assoc_setup(picks, fs, cable_pos, c0, xs, ys, z, dt, t0_range)
+    d, nch, nx, ny, nbins, packed, K = a.device, a.nch, a.nx, a.ny, r.nbins, t.packed, t.packed.shape[1]
     lib = _lib.lib
     with torch.cuda.device(d):
-        stream = dev.stream_ptr(cable)
+        stream = dev.stream_ptr(a.cable)
         votes = torch.empty((ny, nx, nbins), dtype=torch.int32, device=d)
         Ti = torch.empty((max_calls, nch), dtype=torch.float64, device=d)
         fg = torch.empty((max_calls, 4), dtype=torch.float64, device=d)
@@ -467,72 +561,40 @@ def associate_picks(picks, fs, cable_pos, c0, xs, ys, z, dt, min_picks, max_call
         off = torch.empty(nch, dtype=torch.int64, device=d)
         summ = torch.empty(2, dtype=torch.int64, device=d)
         ws = torch.empty(lib.d4w_assoc_best_ws_bytes(), dtype=torch.uint8, device=d)
-        _lib.check(lib.d4w_pick_offsets_i64(dev.ptr(counts), nch, dev.out_ptr(off), dev.out_ptr(summ), stream))
-        _vote(packed, None, 1, 0, cable, fs, c0, gx, gy, z, lo, dt, nbins, votes, None)
+
+        def vote(idx, sign, accumulate, stop):
+            _vote(packed, idx, sign, accumulate, a.cable, a.fs, a.c0, a.gx, a.gy, a.z, r.lo, a.dt, nbins, votes, stop)
+
+        _lib.check(lib.d4w_pick_offsets_i64(dev.ptr(t.counts), nch, dev.out_ptr(off), dev.out_ptr(summ), stream))
+        vote(None, 1, 0, None)
         for c in range(max_calls if K else 0):                   # no host synchronisation and no torch kernel in here
             _lib.check(lib.d4w_assoc_best_i32(dev.ptr(votes), nx, ny, nbins, min_picks, c, dev.out_ptr(state), dev.out_ptr(rec),
                                               dev.out_ptr(ws), stream))
-            _lib.check(lib.d4w_assoc_select_f64(dev.ptr(packed), K, dev.ptr(off), dev.ptr(cable), nch, fs, c0, dev.ptr(gx), nx,
-                                                dev.ptr(gy), ny, z, lo, dt, nbins, c, dev.ptr(state), dev.out_ptr(rec),
+            _lib.check(lib.d4w_assoc_select_f64(dev.ptr(packed), K, dev.ptr(off), dev.ptr(a.cable), nch, a.fs, a.c0, dev.ptr(a.gx), nx,
+                                                dev.ptr(a.gy), ny, a.z, r.lo, a.dt, nbins, c, dev.ptr(state), dev.out_ptr(rec),
                                                 dev.out_ptr(assigned), dev.out_ptr(Ti), dev.out_ptr(chosen), dev.out_ptr(e_chosen),
                                                 dev.out_ptr(fg), stream))
-            _vote(packed, chosen, -1, 1, cable, fs, c0, gx, gy, z, lo, dt, nbins, votes, state)
+            vote(chosen, -1, 1, state)
         ncalls = int(state[1].item()) if K and max_calls else 0  # the call's one host read
-        if order is not None:
+        if t.order is not None:
             inv = torch.empty(K, dtype=torch.int64, device=d)
-            inv[torch.from_numpy(order).to(d)] = torch.arange(K, dtype=torch.int64, device=d)
+            inv[torch.from_numpy(t.order).to(d)] = torch.arange(K, dtype=torch.int64, device=d)
             assigned = assigned[inv]                             # row j of the caller's table is row inv[j] of the sorted one
     info = {"first_guess": fg[:ncalls], "node": rec[:ncalls, 0].contiguous(), "bin": rec[:ncalls, 1].contiguous(),
             "score": rec[:ncalls, 2].contiguous(), "npicks": rec[:ncalls, 3].contiguous(), "assigned": assigned,
-            "edges": torch.from_numpy(edges).to(d)}
+            "edges": torch.from_numpy(r.edges).to(d)}
     if return_votes:
         info["votes"] = votes
-    return _out(Ti[:ncalls], as_tensor), {k: _out(v, as_tensor) for k, v in info.items()}
+    return _out(Ti[:ncalls], a.as_tensor), {k: _out(v, a.as_tensor) for k, v in info.items()}
 
 
 # ------------------------------------------------------------------------------------------
 # beyond the reference: delay-and-sum stack of envelopes on the position grid (csrc/stack.hip)
 # ------------------------------------------------------------------------------------------
-def _pos_finite(**kw):
-    for name, v in kw.items():
-        if not (np.isfinite(v) and v > 0):
-            raise ValueError("%s must be positive and finite, got %r" % (name, v))
-
-
-def _grid_axes(xs, ys, device):
-    gx, gy = _f64(xs, device).reshape(-1), _f64(ys, device).reshape(-1)
-    if gx.numel() < 1 or gy.numel() < 1:
-        raise ValueError("the grid needs at least one node")
-    return gx, gy
-
-
-def _env_block(env, device):
-    """(float32 CUDA tensor [nch x ns] with unit column stride, row pitch in elements).  A column-sliced float32 CUDA view is
-    taken as it is; everything else becomes a contiguous float32 copy on the device."""
-    if getattr(env, "ndim", 0) != 2:
-        raise ValueError("env must be a 2-D [channel x time] array")
-    if env.shape[0] < 1 or env.shape[1] < 1:
-        raise ValueError("env must not be empty, got %s" % (tuple(env.shape),))
-    if (dev.is_tensor(env) and env.is_cuda and env.dtype == torch.float32 and (device is None or env.device == torch.device(device))
-            and env.stride(1) == 1 and (env.stride(0) >= env.shape[1] or env.shape[0] == 1)):
-        return env, (env.stride(0) if env.shape[0] > 1 else env.shape[1])
-    e = dev.to_device_f32(env, device)
-    return e, e.shape[1]
-
-
-def _weights(weights, nch, device):
-    if weights is None:
-        return None
-    w = dev.to_device_f32(weights if dev.is_tensor(weights) else np.asarray(weights).reshape(1, -1), device).reshape(-1)
-    if w.numel() != nch:
-        raise ValueError("weights must hold one value per channel (%d), got %d" % (nch, w.numel()))
-    return w
-
-
-def _delays(cable, c0, fs, gx, gy, z):
-    d = torch.empty((gy.numel(), gx.numel(), cable.shape[0]), dtype=torch.int32, device=cable.device)
-    _lib.check(_lib.lib.d4w_stack_delays_i32(dev.ptr(cable), cable.shape[0], c0, fs, dev.ptr(gx), gx.numel(), dev.ptr(gy), gy.numel(), z,
-                                             dev.out_ptr(d), dev.stream_ptr(cable)))
+def _delays(a, z):
+    d = torch.empty((a.ny, a.nx, a.nch), dtype=torch.int32, device=a.device)
+    _lib.check(_lib.lib.d4w_stack_delays_i32(dev.ptr(a.cable), a.nch, a.c0, a.fs, dev.ptr(a.gx), a.nx, dev.ptr(a.gy), a.ny, z,
+                                             dev.out_ptr(d), dev.stream_ptr(a.cable)))
     return d
 
 
@@ -540,13 +602,11 @@ def delay_table(cable_pos, c0, fs, xs, ys, z):
     """Travel times in samples from every node (xs[ix], ys[iy], z) to every channel, int32 [ny x nx x channel]:
     d = floor(|cable_pos[ch] - node| (1 / c0) fs + 0.5) in float64.  The table stack_grid sums along; it depends on the
     geometry and the rate only, so keep it for the consecutive files of one cable (stack_grid(..., delays=table))."""
-    cable = _cable(cable_pos, _device_of(cable_pos, xs, ys))
-    gx, gy = _grid_axes(xs, ys, cable.device)
-    c0, fs, z = float(c0), float(fs), float(z)
-    _pos_finite(c0=c0, fs=fs)
-    with torch.cuda.device(cable.device):
-        d = _delays(cable, c0, fs, gx, gy, z)
-    return _out(d, any(dev.is_tensor(a) for a in (cable_pos, xs, ys)))
+    z = float(z)
+    a = _upload(_check(cable_pos, c0, fs, xs=xs, ys=ys))
+    with torch.cuda.device(a.device):
+        d = _delays(a, z)
+    return _out(d, a.as_tensor)
 
 
 def _stack(e, pitch, table, w, nx, ny, k0, k1, normalize, form=0):
@@ -559,11 +619,24 @@ def _stack(e, pitch, table, w, nx, ny, k0, k1, normalize, form=0):
     return out, info
 
 
-def _k_range(k_range, ns):
-    k0, k1 = (0, ns) if k_range is None else (int(k_range[0]), int(k_range[1]))
-    if not k0 < k1:
+def _stack_grid(env, fs, cable_pos, c0, xs, ys, z, weights, k_range, normalize, delays=None):
+    """stack_grid on the device, shared with locate_stack: (the arguments with z, stack [ny x nx x nt], times as an ndarray)."""
+    k0, k1 = (0, None) if k_range is None else (int(k_range[0]), int(k_range[1]))
+    if k_range is not None and not k0 < k1:
         raise ValueError("k_range = (k0, k1) must have k0 < k1, got (%d, %d)" % (k0, k1))
-    return k0, k1
+    a = _check(cable_pos, c0, fs, block=env, weights=weights, xs=xs, ys=ys)
+    a.z = float(z)
+    if delays is not None and _shape(delays) != (a.ny, a.nx, a.nch):
+        raise ValueError("delays must be [ny x nx x channel] = %s, got %s" % ((a.ny, a.nx, a.nch), _shape(delays)))
+    _upload(a, like=(delays,))
+    k1 = a.ns if k1 is None else k1
+    with torch.cuda.device(a.device):
+        if delays is None:
+            table = _delays(a, a.z)
+        else:
+            table = (delays if dev.is_tensor(delays) else torch.from_numpy(np.ascontiguousarray(delays))).to(a.device, torch.int32).contiguous()
+        stack, _ = _stack(a.e, a.pitch, table, a.w, a.nx, a.ny, k0, k1, normalize)
+    return a, stack, np.arange(k0, k1) / a.fs
 
 
 def stack_grid(env, fs, cable_pos, c0, xs, ys, z, weights=None, k_range=None, normalize=False, *, delays=None):
@@ -582,28 +655,8 @@ def stack_grid(env, fs, cable_pos, c0, xs, ys, z, weights=None, k_range=None, no
     delays: the table of delay_table for this cable, grid, c0 and fs (built here when None).
     float32 sums in increasing channel order, one thread per element: run-to-run bit-identical.  NumPy in -> NumPy out; a
     CUDA tensor in -> tensors on that device and stream."""
-    device = _device_of(env, cable_pos, xs, ys, weights, delays)
-    cable = _cable(cable_pos, device)
-    gx, gy = _grid_axes(xs, ys, cable.device)
-    c0, fs, z = float(c0), float(fs), float(z)
-    _pos_finite(c0=c0, fs=fs)
-    e, pitch = _env_block(env, cable.device)
-    nch, ns = e.shape
-    if nch != cable.shape[0]:
-        raise ValueError("env has %d rows, cable_pos %d channels" % (nch, cable.shape[0]))
-    k0, k1 = _k_range(k_range, ns)
-    w = _weights(weights, nch, cable.device)
-    as_tensor = any(dev.is_tensor(a) for a in (env, cable_pos, xs, ys, weights, delays))
-    with torch.cuda.device(cable.device):
-        if delays is None:
-            table = _delays(cable, c0, fs, gx, gy, z)
-        else:
-            table = (delays if dev.is_tensor(delays) else torch.from_numpy(np.ascontiguousarray(delays))).to(cable.device, torch.int32).contiguous()
-            if tuple(table.shape) != (gy.numel(), gx.numel(), nch):
-                raise ValueError("delays must be [ny x nx x channel] = %s, got %s" % ((gy.numel(), gx.numel(), nch), tuple(table.shape)))
-        out, _ = _stack(e, pitch, table, w, gx.numel(), gy.numel(), k0, k1, normalize)
-    times = np.arange(k0, k1) / fs
-    return _out(out, as_tensor), (torch.from_numpy(times).to(cable.device) if as_tensor else times)
+    a, out, times = _stack_grid(env, fs, cable_pos, c0, xs, ys, z, weights, k_range, normalize, delays)
+    return _out(out, a.as_tensor), (torch.from_numpy(times).to(a.device) if a.as_tensor else times)
 
 
 def _best(s):
@@ -626,18 +679,23 @@ def stack_best(stack):
     return _out(peak, as_tensor), _out(node, as_tensor)
 
 
-def _arrivals(e, pitch, fs, cable, c0, p, t, h, threshold, w):
-    ncalls, nch = p.shape[0], cable.shape[0]
-    Ti = torch.empty((ncalls, nch), dtype=torch.float64, device=cable.device)
+def _per_channel(threshold, nch):
+    """Whether `threshold` is one value per channel rather than a scalar; checked on the host."""
     per_channel = dev.is_tensor(threshold) or np.ndim(threshold) > 0
-    thr = None
-    if per_channel:
-        thr = _f64(threshold, cable.device).reshape(-1)
-        if thr.numel() != nch:
-            raise ValueError("threshold must be a scalar or one value per channel (%d), got %d" % (nch, thr.numel()))
-    _lib.check(_lib.lib.d4w_stack_arrivals_f64(dev.ptr(e), pitch, nch, e.shape[1], fs, dev.ptr(cable), c0, dev.ptr(p), dev.ptr(t), ncalls, h,
-                                               0.0 if per_channel else float(threshold), dev.ptr(thr) if per_channel else None,
-                                               dev.ptr(w) if w is not None else None, dev.out_ptr(Ti), dev.stream_ptr(cable)))
+    if per_channel and _count(threshold) != nch:
+        raise ValueError("threshold must be a scalar or one value per channel (%d), got %d" % (nch, _count(threshold)))
+    return per_channel
+
+
+def _arrivals(a, p, t, h, threshold):
+    """arrivals_near on the device, shared with locate_stack: Ti [ncalls x nch] for the calls at p [ncalls x 3], t [ncalls]."""
+    ncalls = p.shape[0]
+    Ti = torch.empty((ncalls, a.nch), dtype=torch.float64, device=a.device)
+    if ncalls:
+        thr = _f64(threshold, a.device).reshape(-1) if _per_channel(threshold, a.nch) else None
+        _lib.check(_lib.lib.d4w_stack_arrivals_f64(dev.ptr(a.e), a.pitch, a.nch, a.ns, a.fs, dev.ptr(a.cable), a.c0, dev.ptr(p), dev.ptr(t), ncalls,
+                                                   h, 0.0 if thr is not None else float(threshold), dev.ptr(thr) if thr is not None else None,
+                                                   dev.ptr(a.w) if a.w is not None else None, dev.out_ptr(Ti), dev.stream_ptr(a.cable)))
     return Ti
 
 
@@ -648,34 +706,16 @@ def arrivals_near(env, fs, cable_pos, c0, pos, t0, halfwidth, threshold, weights
     Returns Ti [ncalls x channel] float64 = sample / fs, NaN where the window misses the record, weights[ch] = 0, or the
     maximum is below `threshold` (a scalar or one value per channel): the form associate_picks returns and solve_lq_batch
     takes.  pos: [ncalls x 3] (or [3] with a scalar t0: one call, Ti still [1 x channel])."""
-    device = _device_of(env, cable_pos, pos, t0, weights)
-    cable = _cable(cable_pos, device)
-    c0, fs = float(c0), float(fs)
-    _pos_finite(c0=c0, fs=fs)
     h = int(halfwidth)
     if h < 0 or h != halfwidth:
         raise ValueError("halfwidth must be a non-negative number of samples")
-    e, pitch = _env_block(env, cable.device)
-    nch = cable.shape[0]
-    if e.shape[0] != nch:
-        raise ValueError("env has %d rows, cable_pos %d channels" % (e.shape[0], nch))
-    p = _f64(pos, cable.device)
-    p = p.reshape(1, -1) if p.dim() == 1 else p
-    if p.dim() != 2 or p.shape[1] != 3:
-        raise ValueError("pos must be [x, y, z] or [ncalls x 3], got %s" % (tuple(p.shape),))
-    t = _f64(t0, cable.device).reshape(-1)
-    if t.numel() == 1 and p.shape[0] != 1:
-        t = t.expand(p.shape[0]).contiguous()
-    if t.numel() != p.shape[0]:
-        raise ValueError("t0 must be a scalar or one value per call")
-    w = _weights(weights, nch, cable.device)
-    as_tensor = any(dev.is_tensor(a) for a in (env, cable_pos, pos, t0, weights))
-    with torch.cuda.device(cable.device):
-        if p.shape[0] == 0:
-            Ti = torch.empty((0, nch), dtype=torch.float64, device=cable.device)
-        else:
-            Ti = _arrivals(e, pitch, fs, cable, c0, p, t, h, threshold, w)
-    return _out(Ti, as_tensor)
+    a = _check(cable_pos, c0, fs, block=env, weights=weights, pos=pos, t0=t0)
+    if a.ncalls:
+        _per_channel(threshold, a.nch)
+    _upload(a)
+    with torch.cuda.device(a.device):
+        Ti = _arrivals(a, a.p, a.t, h, threshold)
+    return _out(Ti, a.as_tensor)
 
 
 def locate_stack(env, fs, cable_pos, c0, xs, ys, z, threshold, halfwidth, pick_threshold, max_calls=64, weights=None, k_range=None,
@@ -700,23 +740,9 @@ def locate_stack(env, fs, cable_pos, c0, xs, ys, z, threshold, halfwidth, pick_t
         raise ValueError("max_calls must not be negative")
     if int(halfwidth) < 0:
         raise ValueError("halfwidth must be a non-negative number of samples")
-    device = _device_of(env, cable_pos, xs, ys, weights)
-    cable = _cable(cable_pos, device)
-    gx, gy = _grid_axes(xs, ys, cable.device)
-    c0, fs, z = float(c0), float(fs), float(z)
-    _pos_finite(c0=c0, fs=fs)
-    e, pitch = _env_block(env, cable.device)
-    nch, ns = e.shape
-    if nch != cable.shape[0]:
-        raise ValueError("env has %d rows, cable_pos %d channels" % (nch, cable.shape[0]))
-    k0, k1 = _k_range(k_range, ns)
-    w = _weights(weights, nch, cable.device)
-    as_tensor = any(dev.is_tensor(a) for a in (env, cable_pos, xs, ys, weights))
-    d, nx = cable.device, gx.numel()
-    times = np.arange(k0, k1) / fs
+    a, stack, times = _stack_grid(env, fs, cable_pos, c0, xs, ys, z, weights, k_range, normalize)
+    d, nx = a.device, a.nx
     with torch.cuda.device(d):
-        table = _delays(cable, c0, fs, gx, gy, z)
-        stack, _ = _stack(e, pitch, table, w, nx, gy.numel(), k0, k1, normalize)
         peak, best_node = _best(stack)
         cols = detect.pick_times(peak[None, :], threshold).packed[1].cpu().numpy()
         peak_h, node_h = peak.cpu().numpy(), best_node.cpu().numpy()
@@ -726,19 +752,16 @@ def locate_stack(env, fs, cable_pos, c0, xs, ys, z, threshold, halfwidth, pick_t
         cols = np.sort(cols)
         nodes = node_h[cols].astype(np.int64)
         fg = np.empty((len(cols), 4))
-        fg[:, 0], fg[:, 1] = gx.cpu().numpy()[nodes % nx], gy.cpu().numpy()[nodes // nx]
-        fg[:, 2], fg[:, 3] = z, times[cols]
+        fg[:, 0], fg[:, 1] = a.gx.cpu().numpy()[nodes % nx], a.gy.cpu().numpy()[nodes // nx]
+        fg[:, 2], fg[:, 3] = a.z, times[cols]
         fg_d = torch.from_numpy(fg).to(d)
-        if len(cols):
-            Ti = _arrivals(e, pitch, fs, cable, c0, fg_d[:, :3].contiguous(), fg_d[:, 3].contiguous(), int(halfwidth), pick_threshold, w)
-        else:
-            Ti = torch.empty((0, nch), dtype=torch.float64, device=d)
+        Ti = _arrivals(a, fg_d[:, :3].contiguous(), fg_d[:, 3].contiguous(), int(halfwidth), pick_threshold)
         info = {"first_guess": fg_d, "node": torch.from_numpy(nodes.astype(np.int32)).to(d),
                 "column": torch.from_numpy(cols.astype(np.int32)).to(d), "value": torch.from_numpy(peak_h[cols]).to(d),
                 "npicks": (~torch.isnan(Ti)).sum(1).to(torch.int32), "times": torch.from_numpy(times).to(d)}
         if return_stack:
             info.update(stack=stack, peak=peak, best_node=best_node)
-    return _out(Ti, as_tensor), {k: _out(v, as_tensor) for k, v in info.items()}
+    return _out(Ti, a.as_tensor), {k: _out(v, a.as_tensor) for k, v in info.items()}
 
 
 # ------------------------------------------------------------------------------------------
@@ -746,31 +769,31 @@ def locate_stack(env, fs, cable_pos, c0, xs, ys, z, threshold, halfwidth, pick_t
 # ------------------------------------------------------------------------------------------
 def beam_limits():
     """(largest ncalls of a call, largest length, channels per summation segment, samples per workgroup) of the beam kernel."""
-    import ctypes
     a, b, s, t = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     _lib.check(_lib.lib.d4w_beam_limits(ctypes.byref(a), ctypes.byref(b), ctypes.byref(s)))
     _lib.check(_lib.lib.d4w_beam_tile(ctypes.byref(t)))
     return a.value, b.value, s.value, t.value
 
 
-def _positions(pos, device):
-    p = _f64(pos, device)
-    return p.reshape(1, -1) if p.dim() == 1 else p
+def _beam_args(cable_pos, c0, fs, pos, **kw):
+    """_check for beam_delays and beamform: the batch of positions must fit one launch as well."""
+    a = _check(cable_pos, c0, fs, pos=pos, **kw)
+    if a.ncalls > beam_limits()[0]:
+        raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, beam_limits()[0]))
+    return a
 
 
-def _beam_delays(cable, c0, fs, p, rounded):
-    ncalls, nch = p.shape[0], cable.shape[0]
-    if rounded:
-        r = torch.empty((ncalls, nch), dtype=torch.int32, device=cable.device)
-        if ncalls:
-            _lib.check(_lib.lib.d4w_beam_delays(dev.ptr(cable), nch, c0, fs, dev.ptr(p), ncalls, None, None, dev.out_ptr(r), dev.stream_ptr(cable)))
-        return r
-    k = torch.empty((ncalls, nch), dtype=torch.int32, device=cable.device)
-    f = torch.empty((ncalls, nch), dtype=torch.float32, device=cable.device)
-    if ncalls:
-        _lib.check(_lib.lib.d4w_beam_delays(dev.ptr(cable), nch, c0, fs, dev.ptr(p), ncalls, dev.out_ptr(k), dev.out_ptr(f), None,
-                                            dev.stream_ptr(cable)))
-    return k, f
+def _beam_delays(a, rounded):
+    """r (rounded) or (k, f), each [ncalls x nch], for the positions a.p."""
+    shape = (a.ncalls, a.nch)
+    r = torch.empty(shape, dtype=torch.int32, device=a.device) if rounded else None
+    k = None if rounded else torch.empty(shape, dtype=torch.int32, device=a.device)
+    f = None if rounded else torch.empty(shape, dtype=torch.float32, device=a.device)
+    if a.ncalls:
+        _lib.check(_lib.lib.d4w_beam_delays(dev.ptr(a.cable), a.nch, a.c0, a.fs, dev.ptr(a.p), a.ncalls, dev.out_ptr(k) if k is not None else None,
+                                            dev.out_ptr(f) if f is not None else None, dev.out_ptr(r) if r is not None else None,
+                                            dev.stream_ptr(a.cable)))
+    return r if rounded else (k, f)
 
 
 def beam_delays(cable_pos, c0, fs, pos, rounded=False):
@@ -782,14 +805,10 @@ def beam_delays(cable_pos, c0, fs, pos, rounded=False):
     a NaN lands as well): what beamform(order=0, delays=...) takes.
     The tables depend on the geometry, the rate and the positions only.  NumPy in -> NumPy out; a CUDA tensor in -> tensors on that
     device and stream."""
-    _beam_geometry(cable_pos, c0, fs, pos)
-    c0, fs = float(c0), float(fs)
-    cable = _cable(cable_pos, _device_of(cable_pos, pos))
-    p = _positions(pos, cable.device)
-    as_tensor = any(dev.is_tensor(a) for a in (cable_pos, pos))
-    with torch.cuda.device(cable.device):
-        d = _beam_delays(cable, c0, fs, p, bool(rounded))
-    return _out(d, as_tensor) if rounded else (_out(d[0], as_tensor), _out(d[1], as_tensor))
+    a = _upload(_beam_args(cable_pos, c0, fs, pos))
+    with torch.cuda.device(a.device):
+        d = _beam_delays(a, bool(rounded))
+    return _out(d, a.as_tensor) if rounded else (_out(d[0], a.as_tensor), _out(d[1], a.as_tensor))
 
 
 def _given_table(t, device):
@@ -797,57 +816,18 @@ def _given_table(t, device):
     return t.to(device).contiguous()
 
 
-def _shape(a):
-    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
-
-
-def _dtype_name(a):
-    return str(a.dtype).split(".")[-1] if hasattr(a, "dtype") else str(np.asarray(a).dtype)
-
-
-def _beam_geometry(cable_pos, c0, fs, pos):
-    """The checks beam_delays and beamform share, on the host before any device work: (channels, calls)."""
-    _pos_finite(c0=float(c0), fs=float(fs))
-    cs, ps = _shape(cable_pos), _shape(pos)
-    if len(cs) != 2 or cs[1] != 3 or cs[0] < 1:
-        raise ValueError("cable_pos must be [channel x 3], got %s" % (cs,))
-    if ps != (3,) and (len(ps) != 2 or ps[1] != 3):
-        raise ValueError("pos must be [x, y, z] or [ncalls x 3], got %s" % (ps,))
-    ncalls = 1 if len(ps) == 1 else ps[0]
-    if ncalls > beam_limits()[0]:
-        raise ValueError("%d calls are more than the %d one launch takes" % (ncalls, beam_limits()[0]))
-    return cs[0], ncalls
-
-
-def _beam_check(trace, fs, cable_pos, c0, pos, start, length, order, weights, next_block, delays):
-    """Every argument of beamform against the others, on the host before any device work:
-    (order, channels, samples, calls, length, the given delay tables as a tuple)."""
-    if isinstance(order, bool) or order not in (0, 1, 3):
-        raise ValueError("order must be 0, 1 or 3, got %r" % (order,))
-    order = int(order)
-    nch, ncalls = _beam_geometry(cable_pos, c0, fs, pos)
-    ts = _shape(trace)
-    if len(ts) != 2 or ts[0] < 1 or ts[1] < 1:
-        raise ValueError("trace must be a non-empty 2-D [channel x time] array, got %s" % (ts,))
-    if ts[0] != nch:
-        raise ValueError("trace has %d rows, cable_pos %d channels" % (ts[0], nch))
-    if next_block is not None:
-        bs = _shape(next_block)
-        if len(bs) != 2 or bs[1] < 1:
-            raise ValueError("next_block must be a non-empty 2-D [channel x time] array, got %s" % (bs,))
-        if bs[0] != nch:
-            raise ValueError("next_block has %d rows, trace %d" % (bs[0], nch))
-    nt = ts[1] if length is None else length
+def _beam_check(a, start, length, order, delays):
+    """The arguments only beamform has against the shared ones, on the host before any device work:
+    (length, the given delay tables as a tuple)."""
+    nt = a.ns if length is None else length
     if isinstance(nt, bool) or nt != int(nt) or nt < 1:
         raise ValueError("length must be a positive number of samples, got %r" % (length,))
     nt = int(nt)
     if nt > beam_limits()[1]:
         raise ValueError("length %d is more than the %d one launch takes" % (nt, beam_limits()[1]))
     ss = _shape(start)
-    if ss not in ((), (ncalls,)) or _dtype_name(start)[:3] not in ("int", "uin"):
-        raise ValueError("start must be an int or [ncalls] = (%d,) ints, got shape %s of %s" % (ncalls, ss, _dtype_name(start)))
-    if weights is not None and int(np.prod(_shape(weights))) != nch:
-        raise ValueError("weights must hold one value per channel (%d), got shape %s" % (nch, _shape(weights)))
+    if ss not in ((), (a.ncalls,)) or _dtype_name(start)[:3] not in ("int", "uin"):
+        raise ValueError("start must be an int or [ncalls] = (%d,) ints, got shape %s of %s" % (a.ncalls, ss, _dtype_name(start)))
     tables = ()
     if delays is not None:
         tables = (delays,) if order == 0 else tuple(delays)
@@ -855,24 +835,24 @@ def _beam_check(trace, fs, cable_pos, c0, pos, start, length, order, weights, ne
         if len(tables) != len(want):
             raise ValueError("delays must be (k, f) for order %d" % order)
         for t, (name, dtype) in zip(tables, want):
-            if _shape(t) != (ncalls, nch) or _dtype_name(t) != dtype:
-                raise ValueError("delays: %s must be %s [ncalls x channel] = %s, got %s %s" % (name, dtype, (ncalls, nch), _dtype_name(t), _shape(t)))
-    return order, nch, ts[1], ncalls, nt, tables
+            if _shape(t) != (a.ncalls, a.nch) or _dtype_name(t) != dtype:
+                raise ValueError("delays: %s must be %s [ncalls x channel] = %s, got %s %s" % (name, dtype, (a.ncalls, a.nch), _dtype_name(t), _shape(t)))
+    return nt, tables
 
 
-def _beam(e, pitch, nb, pitch_nb, kr, f, w, start, nt, order, normalize):
-    """The kernel on device tensors: beam [ncalls x nt] float32."""
-    import ctypes
-    nch, ns = e.shape
-    ncalls = kr.shape[0]
-    out = torch.empty((ncalls, nt), dtype=torch.float32, device=e.device)
+def _beam(a, kr, f, start, nt, order, normalize):
+    """The kernel on device tensors: beam [ncalls x nt] float32; no launch without a call."""
+    out = torch.empty((a.ncalls, nt), dtype=torch.float32, device=a.device)
+    if not a.ncalls:
+        return out
+    nb, w = a.nb, a.w
     nbytes = ctypes.c_size_t()
-    _lib.check(_lib.lib.d4w_beam_ws_bytes(nch, ncalls, nt, ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=e.device) if nbytes.value else None
-    _lib.check(_lib.lib.d4w_beamform_f32(dev.ptr(e), pitch, nch, ns, dev.ptr(nb) if nb is not None else None, pitch_nb,
+    _lib.check(_lib.lib.d4w_beam_ws_bytes(a.nch, a.ncalls, nt, ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=a.device) if nbytes.value else None
+    _lib.check(_lib.lib.d4w_beamform_f32(dev.ptr(a.e), a.pitch, a.nch, a.ns, dev.ptr(nb) if nb is not None else None, a.pitch_nb,
                                          nb.shape[1] if nb is not None else 0, dev.ptr(kr), dev.ptr(f) if f is not None else None,
-                                         dev.ptr(w) if w is not None else None, dev.ptr(start), ncalls, nt, order, int(bool(normalize)),
-                                         dev.out_ptr(out), dev.out_ptr(ws) if ws is not None else None, dev.stream_ptr(e)))
+                                         dev.ptr(w) if w is not None else None, dev.ptr(start), a.ncalls, nt, order, int(bool(normalize)),
+                                         dev.out_ptr(out), dev.out_ptr(ws) if ws is not None else None, dev.stream_ptr(a.e)))
     return out
 
 
@@ -899,31 +879,26 @@ def beamform(trace, fs, cable_pos, c0, pos, start=0, length=None, order=1, weigh
     float32 sums in increasing channel order in fixed segments of beam_limits()[2] channels, the segment partials added in
     increasing order: run-to-run bit-identical, independent of the other calls of the batch and of a power-of-two scaling of trace.
     NumPy in -> NumPy out; a CUDA tensor in -> tensors on that device and stream."""
-    order, nch, ns, ncalls, nt, tables = _beam_check(trace, fs, cable_pos, c0, pos, start, length, order, weights, next_block, delays)
-    c0, fs = float(c0), float(fs)
-    cable = _cable(cable_pos, _device_of(trace, cable_pos, pos, weights, next_block, start, *tables))
-    e, pitch = _env_block(trace, cable.device)
-    nb, pitch_nb = (None, 0) if next_block is None else _env_block(next_block, cable.device)
-    p = _positions(pos, cable.device)
+    if isinstance(order, bool) or order not in (0, 1, 3):
+        raise ValueError("order must be 0, 1 or 3, got %r" % (order,))
+    order = int(order)
+    a = _beam_args(cable_pos, c0, fs, pos, block=trace, name="trace", next_block=next_block, weights=weights)
+    nt, tables = _beam_check(a, start, length, order, delays)
+    _upload(a, like=(start,) + tables)
+    d = a.device
     if dev.is_tensor(start):
-        s = start.to(cable.device, torch.int64).reshape(-1)
+        s = start.to(d, torch.int64).reshape(-1)
     else:
-        s = torch.from_numpy(np.array(start, dtype=np.int64).reshape(-1)).to(cable.device)
-    s = s.expand(ncalls).contiguous()
-    w = _weights(weights, nch, cable.device)
-    as_tensor = any(dev.is_tensor(a) for a in (trace, cable_pos, pos, weights, next_block, start) + tuple(tables))
-    with torch.cuda.device(cable.device):
+        s = torch.from_numpy(np.array(start, dtype=np.int64).reshape(-1)).to(d)
+    s = s.expand(a.ncalls).contiguous()
+    with torch.cuda.device(d):
         if delays is None:
-            d = _beam_delays(cable, c0, fs, p, order == 0)
-            kr, f = (d, None) if order == 0 else d
+            kr, f = (_beam_delays(a, True), None) if order == 0 else _beam_delays(a, False)
         else:
-            kr = _given_table(tables[0], cable.device)
-            f = _given_table(tables[1], cable.device) if order else None
-        if ncalls:
-            out = _beam(e, pitch, nb, pitch_nb, kr, f, w, s, nt, order, normalize)
-        else:
-            out = torch.empty((0, nt), dtype=torch.float32, device=cable.device)
+            kr = _given_table(tables[0], d)
+            f = _given_table(tables[1], d) if order else None
+        out = _beam(a, kr, f, s, nt, order, normalize)
         # a tensor divisor: a true division (by a Python number torch multiplies with the reciprocal instead)
-        times = (s.to(torch.float64)[:, None] + torch.arange(nt, dtype=torch.float64, device=cable.device)[None, :]) \
-            / torch.full((), fs, dtype=torch.float64, device=cable.device)
-    return _out(out, as_tensor), _out(times, as_tensor)
+        times = (s.to(torch.float64)[:, None] + torch.arange(nt, dtype=torch.float64, device=d)[None, :]) \
+            / torch.full((), a.fs, dtype=torch.float64, device=d)
+    return _out(out, a.as_tensor), _out(times, a.as_tensor)

@@ -827,7 +827,8 @@ int d4w_assoc_select_f64(const int64_t* picks, int npicks, const int64_t* offset
  *   env [nch][ns] float32 with a row pitch in ELEMENTS (pitch >= ns: a column-sliced view is read in place), the envelope of
  *     a correlogram; weights [nch] float32, or NULL for ones.
  *   d[g][ch] = (int) floor(|cable_pos[ch] - node_g| * (1 / c0) * fs + 0.5)        travel time in samples, float64, capped
- *     at 2^30; the same difference / square-root expression as the vote, 1 / c0 formed once on the host, no contraction.
+ *     at 2^30; csrc/moveout.h is the single definition of the distance and the delay for the vote, this stack and the beam
+ *     below: differences first, one square root, 1 / c0 formed once on the host, no contraction.
  *   stack[g][k - k0] = sum over ch, in increasing ch, of weights[ch] * env[ch][k + d[g][ch]]             k0 <= k < k1
  *     over the channels with weights[ch] != 0 and 0 <= k + d[g][ch] < ns
  *
@@ -871,8 +872,8 @@ int d4w_stack_arrivals_f64(const float* env, int64_t pitch, int nch, int ns, dou
  * Delay-and-sum beam of the strain toward located calls (das4whales_amd/csrc/beam.hip; the reference has
  * none of this): the waveform of a call with the array's gain.  Every pointer is DEVICE memory unless it returns a limit.
  *
- *   tau[c][ch] = |cable_pos[ch] - pos[c]| * (1 / c0) * fs      the stack's travel-time expression above, float64, 1 / c0
- *     formed once on the host, no contraction; pos [ncalls][3].
+ *   tau[c][ch] = |cable_pos[ch] - pos[c]| * (1 / c0) * fs      the function of csrc/moveout.h the stack's delay rounds, float64,
+ *     1 / c0 formed once on the host, no contraction; pos [ncalls][3].
  *   r = (int) floor(tau + 0.5), capped at 2^30 (a NaN lands on the cap): d4w_stack_delays_i32's value at an arbitrary position.
  *   k = (int) floor(tau), f = (float)(tau - k) in [0, 1); a fraction that rounds to 1.0f is carried into k; at the cap f = 0.
  *   beam[c][j] = sum over ch, in increasing ch, of weights[ch] * v(ch, start[c] + j + delay[c][ch]),     0 <= j < length
