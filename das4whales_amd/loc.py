@@ -6,7 +6,8 @@ the reference does not have; `vote_grid` and `associate_picks` (csrc/assoc.hip) 
 the [ncalls x channel] arrival times these take; `delay_table`, `stack_grid`, `stack_best`, `arrivals_near` and
 `locate_stack` (csrc/stack.hip) get them from the envelopes themselves by a delay-and-sum over the same grid; `beam_delays` and
 `beamform` (csrc/beam.hip) close the chain with the waveform of a located call, the strain of all channels advanced by their
-travel times from the position and summed.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
+travel times from the position and summed; `refine_arrivals` (csrc/align.hip) correlates every channel with that waveform
+around the predicted moveout and returns sub-sample arrival times for a second solve.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
 same device and stream.  The four small per-channel helpers (distances, radii, angles) are host float64 arithmetic for NumPy input, like the
 index arithmetic of the other namespaces; for tensors they stay on the device.
 
@@ -902,3 +903,104 @@ def beamform(trace, fs, cable_pos, c0, pos, start=0, length=None, order=1, weigh
         times = (s.to(torch.float64)[:, None] + torch.arange(nt, dtype=torch.float64, device=d)[None, :]) \
             / torch.full((), a.fs, dtype=torch.float64, device=d)
     return _out(out, a.as_tensor), _out(times, a.as_tensor)
+
+
+# ------------------------------------------------------------------------------------------
+# beyond the reference: arrival times refined by correlating every channel with the beam (csrc/align.hip)
+# ------------------------------------------------------------------------------------------
+def align_limits():
+    """(largest number of calls, largest template length, largest max_lag, channels per workgroup) of the alignment kernel."""
+    a, b, m, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib.d4w_align_limits(ctypes.byref(a), ctypes.byref(b), ctypes.byref(m), ctypes.byref(w)))
+    return a.value, b.value, m.value, w.value
+
+
+def _align_check(a, template, start, max_lag, min_coef, delays):
+    """The arguments only refine_arrivals has against the shared ones, on the host before any device work: (L, M, min_coef)."""
+    max_calls, max_length, max_m, _ = align_limits()
+    if a.ncalls > max_calls:
+        raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, max_calls))
+    ts = _shape(template)
+    if not ((len(ts) == 2 and ts[0] == a.ncalls) or (len(ts) == 1 and a.ncalls == 1)) or _dtype_name(template) != "float32":
+        raise ValueError("template must be float32 [ncalls x L] = (%d, L) (or [L] for one call), got %s %s" % (a.ncalls, _dtype_name(template), ts))
+    L = ts[-1]
+    if L < 1 or L > max_length:
+        raise ValueError("the template length %d is outside 1 .. %d" % (L, max_length))
+    ss = _shape(start)
+    if ss not in ((), (a.ncalls,)) or _dtype_name(start)[:3] not in ("int", "uin"):
+        raise ValueError("start must be an int or [ncalls] = (%d,) ints, got shape %s of %s" % (a.ncalls, ss, _dtype_name(start)))
+    try:
+        whole = not isinstance(max_lag, bool) and _shape(max_lag) == () and int(max_lag) == max_lag and max_lag >= 0
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole:
+        raise ValueError("max_lag must be a non-negative number of samples, got %r" % (max_lag,))
+    if max_lag > max_m:
+        raise ValueError("max_lag %d is more than the %d one launch takes" % (max_lag, max_m))
+    if isinstance(min_coef, bool) or _shape(min_coef) != () or not np.isfinite(min_coef):
+        raise ValueError("min_coef must be a finite number, got %r" % (min_coef,))
+    if delays is not None and (_shape(delays) != (a.ncalls, a.nch) or _dtype_name(delays) != "int32"):
+        raise ValueError("delays must be int32 [ncalls x channel] = %s (beam_delays(rounded=True)), got %s %s"
+                         % ((a.ncalls, a.nch), _dtype_name(delays), _shape(delays)))
+    return L, int(max_lag), float(min_coef)
+
+
+def refine_arrivals(trace, fs, cable_pos, c0, pos, template, start, max_lag, min_coef=0.0, weights=None, next_block=None, subsample=True,
+                    return_all=False, *, delays=None):
+    """Arrival times of located calls refined against their own waveform: every channel is correlated with the call's template
+    (its beam) over the lags -max_lag .. max_lag around the predicted moveout, and the lag of the largest correlation
+    coefficient, moved by a parabola through its two neighbours, becomes the arrival.  With n0 = start[c] + r[c, ch],
+    r = beam_delays(rounded=True):
+        rho[m] = sum_j template[c, j] trace[ch, n0 + m + j] / sqrt(sum_j template[c, j]^2  sum_j trace[ch, n0 + m + j]^2)
+    in float32 for the lags whose L samples all lie inside the record (NaN otherwise; 0 where either energy is 0); m* the lag of
+    the largest non-NaN rho (the smallest of equals), coef = rho[m*]; delta = 0.5 (a - c) / (a - 2 b + c) from
+    a, b, c = rho[m* - 1 .. m* + 1] in float64, clipped to +-0.5, where both neighbours exist, are not NaN and the denominator is
+    negative (else 0; always 0 with subsample=False); Ti[c, ch] = (n0 + m* + delta) / fs.
+    Returns (Ti [ncalls x channel] float64, coef [ncalls x channel] float32); Ti is NaN where weights[ch] = 0, where no lag fits the
+    record or every rho is NaN, or where coef < min_coef: the form associate_picks and arrivals_near return and solve_lq_batch
+    takes, consistent with t0 = start[c] / fs when sample 0 of the template is emission sample start[c] (a beam's is).  With
+    return_all also lag [ncalls x channel] int32 (m*; 0 where there is no lag to report) and rho [ncalls x channel x (2 max_lag + 1)]
+    float32, the table the pick was read from.
+
+    The adaptive-stacking loop this closes:
+        Ti, info = locate_stack(env, fs, cable_pos, c0, xs, ys, z, threshold, halfwidth, pick_threshold)
+        n = solve_lq_batch(Ti, cable_pos, c0, fix_z=True, first_guess=info["first_guess"])
+        start = round(n[:, 3] fs) - lead
+        beam, _ = beamform(trace, fs, cable_pos, c0, n[:, :3], start=start, length=L, order=3)
+        Ti2, coef = refine_arrivals(trace, fs, cable_pos, c0, n[:, :3], beam, start, max_lag=4)
+        n2 = solve_lq_batch(Ti2, cable_pos, c0, fix_z=True, first_guess=n)
+    max_lag must stay under half the dominant period of a narrow-band call, or the largest coefficient skips a cycle: on the
+    64-channel scene of a 20 Hz burst at 200 Hz (period 10 samples) the arrival-time error about its mean is 0.19 samples with
+    max_lag = 4 and 3.4 with max_lag = 10, against 7.9 for envelope-maximum picks (a float64 prototype).
+
+    trace, weights, next_block, start, pos: as for beamform (a CUDA float32 view with unit column stride is read in place; a
+    channel of weight 0 is never read, and its Ti, coef and rho are NaN).  template: float32 [ncalls x L], or [L] for one call.
+    delays: beam_delays(rounded=True) for these positions, built here when None.  Limits: align_limits().
+    The sums are float32 in an order that depends on L alone: run-to-run bit-identical, independent of the other calls of the
+    batch, and rho keeps its bits under a power-of-two scaling of trace or template.  NumPy in -> NumPy out; any tensor in ->
+    tensors on that device and stream."""
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights)
+    L, M, min_coef = _align_check(a, template, start, max_lag, min_coef, delays)
+    _upload(a, like=(start, template, delays))
+    d = a.device
+    if dev.is_tensor(start):
+        s = start.to(d, torch.int64).reshape(-1)
+    else:
+        s = torch.from_numpy(np.array(start, dtype=np.int64).reshape(-1)).to(d)
+    s = s.expand(a.ncalls).contiguous()
+    with torch.cuda.device(d):
+        Ti = torch.empty((a.ncalls, a.nch), dtype=torch.float64, device=d)
+        coef = torch.empty((a.ncalls, a.nch), dtype=torch.float32, device=d)
+        lag = torch.empty((a.ncalls, a.nch), dtype=torch.int32, device=d) if return_all else None
+        rho = torch.empty((a.ncalls, a.nch, 2 * M + 1), dtype=torch.float32, device=d) if return_all else None
+        if a.ncalls:
+            t = _given_table(template, d).reshape(a.ncalls, L)
+            r = _beam_delays(a, True) if delays is None else _given_table(delays, d)
+            nb, w = a.nb, a.w
+            _lib.check(_lib.lib.d4w_align_f32(dev.ptr(a.e), a.pitch, a.nch, a.ns, dev.ptr(nb) if nb is not None else None, a.pitch_nb,
+                                              nb.shape[1] if nb is not None else 0, dev.ptr(t), L, dev.ptr(r), dev.ptr(s), a.ncalls, M,
+                                              dev.ptr(w) if w is not None else None, a.fs, min_coef, int(bool(subsample)), dev.out_ptr(Ti),
+                                              dev.out_ptr(coef), dev.out_ptr(lag) if lag is not None else None,
+                                              dev.out_ptr(rho) if rho is not None else None, dev.stream_ptr(a.e)))
+    out = (Ti, coef) + ((lag, rho) if return_all else ())
+    return tuple(_out(y, a.as_tensor) for y in out)

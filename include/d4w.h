@@ -913,6 +913,44 @@ int d4w_beamform_f32(const float* x, int64_t pitch, int nch, int ns, const float
                      const int32_t* k_or_r, const float* f /* NULL for order 0 */, const float* weights /* or NULL */,
                      const int64_t* start, int ncalls, int length, int order, int normalize, float* beam, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Arrival times refined against the beam (das4whales_amd/csrc/align.hip; the reference has none of this):
+ * every channel correlated with the call's own waveform over 2 max_lag + 1 lags around the predicted moveout.  Every pointer
+ * is DEVICE memory unless it returns a limit.
+ *
+ *   x, xnext, weights, start as for the beam above; tmpl [ncalls][length] float32, one template per call (the beam: its sample
+ *     0 is emission sample start[c]); r [ncalls][nch] int32 = d4w_beam_delays' rounded table.
+ *   n0 = start[c] + r[c][ch] in int64, start clamped to +-2^62.  For every lag m in [-max_lag, max_lag]:
+ *     valid iff the samples n0 + m .. n0 + m + length - 1 all lie inside the record of ns + ns_next samples;
+ *     dot[m] = sum_j tmpl[c][j] x[ch][n0 + m + j],  en[m] = sum_j x[ch][n0 + m + j]^2,  tn[c] = sum_j tmpl[c][j]^2;
+ *     rho[m] = dot / sqrtf(tn en) in float32; 0 where the lag is valid but tn or en is 0; NaN where the lag is not valid (a
+ *     NaN among the samples or in the template makes its entries NaN as well).
+ *   The sums are float32 multiply-adds in an order that depends on length alone: dot and en one chain each over increasing j
+ *   from 0; tn 64 interleaved chains (chain i over j = i, i + 64, ...) added pairwise at distances 32, 16, 8, 4, 2, 1.  rho is
+ *   run-to-run bit-identical, does not depend on the other calls of the batch, and keeps its bits under a power-of-two
+ *   scaling of x or of tmpl.
+ *   m* = the lag of the largest non-NaN rho, the smallest m of equal values; coef = rho[m*].
+ *   delta, in float64 from the float32 a = rho[m* - 1], b = rho[m*], c = rho[m* + 1]: 0.5 (a - c) / den clipped to [-0.5, 0.5]
+ *     where subsample != 0, both neighbours lie within the lags and are not NaN, and den = (a - 2.0 b) + c < 0; otherwise 0.
+ *   Ti[c][ch] = ((double)(n0 + m*) + delta) / fs, a true division, no contraction: the form d4w_loc_solve_f64 takes.  NaN
+ *     where weights[ch] = 0, where no lag is valid or every rho is NaN, or where coef < min_coef.
+ *   A channel of weight 0 is not read at all: its Ti, coef and rho row are NaN and its lag is 0.
+ *
+ * d4w_align_limits: the largest ncalls (65535), template length (4096) and max_lag (255) of a call, and the channels one
+ *   workgroup takes (4; what the tests size their shapes by).
+ * d4w_align_f32: Ti [ncalls][nch] float64 and coef [ncalls][nch] float32; lag [ncalls][nch] int32 = m* (0 where there is no
+ *   lag to report: weight 0, no valid lag, every rho NaN) and rho [ncalls][nch][2 max_lag + 1] float32, each or NULL.  The
+ *   pick reads the float32 rho exactly as stored in the table.  One wave per four channels of a call, no atomics.
+ * Errors: D4W_EINVAL for a NULL required pointer, nch, ns or ncalls < 1, ncalls, length or max_lag beyond the limits,
+ *   length < 1, max_lag < 0, pitch < ns, xnext with ns_next < 1 or pitch_next < ns_next, ns_next != 0 without xnext, fs not
+ *   finite or <= 0, min_coef not finite.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_align_limits(int* max_calls, int* max_length, int* max_lag, int* channels);
+int d4w_align_f32(const float* x, int64_t pitch, int nch, int ns, const float* xnext /* or NULL */, int64_t pitch_next, int ns_next,
+                  const float* tmpl, int length, const int32_t* r, const int64_t* start, int ncalls, int max_lag,
+                  const float* weights /* or NULL */, double fs, double min_coef, int subsample, double* Ti, float* coef,
+                  int32_t* lag /* or NULL */, float* rho /* or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
