@@ -7,7 +7,8 @@ the [ncalls x channel] arrival times these take; `delay_table`, `stack_grid`, `s
 `locate_stack` (csrc/stack.hip) get them from the envelopes themselves by a delay-and-sum over the same grid; `beam_delays` and
 `beamform` (csrc/beam.hip) close the chain with the waveform of a located call, the strain of all channels advanced by their
 travel times from the position and summed; `refine_arrivals` (csrc/align.hip) correlates every channel with that waveform
-around the predicted moveout and returns sub-sample arrival times for a second solve.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
+around the predicted moveout and returns sub-sample arrival times for a second solve; `solve_robust_batch` (csrc/robust.hip) is
+that solve, with per-channel weights and a robust loss, and `relocate` the loop beam -> re-pick -> relocate as one call.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
 same device and stream.  The four small per-channel helpers (distances, radii, angles) are host float64 arithmetic for NumPy input, like the
 index arithmetic of the other namespaces; for tensors they stay on the device.
 
@@ -969,6 +970,8 @@ def refine_arrivals(trace, fs, cable_pos, c0, pos, template, start, max_lag, min
         beam, _ = beamform(trace, fs, cable_pos, c0, n[:, :3], start=start, length=L, order=3)
         Ti2, coef = refine_arrivals(trace, fs, cable_pos, c0, n[:, :3], beam, start, max_lag=4)
         n2 = solve_lq_batch(Ti2, cable_pos, c0, fix_z=True, first_guess=n)
+    The last three lines, with coef as the second solve's weights and a robust loss against the channels that skipped a cycle,
+    are one call: relocate(trace, fs, cable_pos, c0, n, length=L, max_lag=4, lead=lead) (solve_robust_batch).
     max_lag must stay under half the dominant period of a narrow-band call, or the largest coefficient skips a cycle: on the
     64-channel scene of a 20 Hz burst at 200 Hz (period 10 samples) the arrival-time error about its mean is 0.19 samples with
     max_lag = 4 and 3.4 with max_lag = 10, against 7.9 for envelope-maximum picks (a float64 prototype).
@@ -1004,3 +1007,187 @@ def refine_arrivals(trace, fs, cable_pos, c0, pos, template, start, max_lag, min
                                               dev.out_ptr(rho) if rho is not None else None, dev.stream_ptr(a.e)))
     out = (Ti, coef) + ((lag, rho) if return_all else ())
     return tuple(_out(y, a.as_tensor) for y in out)
+
+
+# ------------------------------------------------------------------------------------------
+# beyond the reference: robust weighted relocation (csrc/robust.hip) and the adaptive-stacking loop as one call
+# ------------------------------------------------------------------------------------------
+_LOSSES = {"l2": (0, 1.0), "huber": (1, 1.345), "bisquare": (2, 4.685)}      # name -> (code of the C ABI, default tuning)
+_MAX_NBITER = 100000
+
+
+def robust_limits():
+    """(channels of a call whose |residuals| stay in LDS for the median -- above it they go through a global workspace --,
+    bits one pass of the radix select resolves) of the robust solver."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib.d4w_loc_robust_limits(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def _whole(v, name, lo, hi=None):
+    """v as an int within lo .. hi, checked on the host."""
+    try:
+        ok = not isinstance(v, bool) and _shape(v) == () and int(v) == v and v >= lo and (hi is None or v <= hi)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("%s must be a whole number of at least %d%s, got %r" % (name, lo, "" if hi is None else " and at most %d" % hi, v))
+    return int(v)
+
+
+def _robust_check(Ti, cable_pos, c0, weights, loss, tuning, scale, Nbiter, warmup, first_guess):
+    """Every check of solve_robust_batch on the host, before any device work: (nch, ncalls, loss code, tuning, scale or 0.0,
+    Nbiter, warmup, whether the weights are per call)."""
+    nch = _channels(cable_pos)
+    _pos_finite(c0=float(c0))
+    ts = _shape(Ti)
+    if len(ts) != 2 or ts[1] != nch:
+        raise ValueError("Ti must be [ncalls x channel] with %d channels, got %s" % (nch, ts))
+    ncalls = ts[0]
+    if not isinstance(loss, str) or loss not in _LOSSES:
+        raise ValueError("loss must be one of %s, got %r" % (sorted(_LOSSES), loss))
+    code, default = _LOSSES[loss]
+    for name, v in (("tuning", tuning), ("scale", scale)):
+        if v is None:
+            continue
+        if isinstance(v, bool) or _shape(v) != () or dev.is_tensor(v):
+            raise ValueError("%s must be None or a positive finite number, got %r" % (name, v))
+        _pos_finite(**{name: float(v)})
+    per_call = False
+    if weights is not None:
+        ws = _shape(weights)
+        if ws not in ((nch,), (ncalls, nch)):
+            raise ValueError("weights must be [channel] = (%d,) or [ncalls x channel] = %s, got %s" % (nch, (ncalls, nch), ws))
+        per_call = len(ws) == 2
+    if first_guess is not None and _shape(first_guess) not in ((4,), (ncalls, 4)):
+        raise ValueError("first_guess must be [x, y, z, t0] or one per call (%d x 4), got %s" % (ncalls, _shape(first_guess)))
+    return (nch, ncalls, code, float(default if tuning is None else tuning), 0.0 if scale is None else float(scale),
+            _whole(Nbiter, "Nbiter", 0, _MAX_NBITER), _whole(warmup, "warmup", 0, 2 ** 31 - 1), per_call)
+
+
+def solve_robust_batch(Ti, cable_pos, c0, weights=None, loss="huber", tuning=None, scale=None, Nbiter=10, warmup=4, fix_z=False,
+                       first_guess=None, return_stats=False):
+    """solve_lq_batch with per-channel weights and a robust loss, by iteratively reweighted least squares inside the same
+    damped Gauss-Newton (csrc/robust.hip, one workgroup per call): the second solve for the arrivals and coefficients of
+    refine_arrivals, where a minority of channels is wrong by a whole period, or carries the pick of another call.
+
+    Ti, cable_pos, c0, Nbiter, fix_z, first_guess: as in solve_lq_batch.  weights: None, [channel] or [ncalls x channel]
+    (float64), e.g. coef ** 2.  Channel ch of call c is USED iff Ti[c, ch] is not NaN and weights[c, ch] > 0: a NaN, zero or
+    negative weight means "not used", and the Ti and the cable row of an unused channel may hold anything.
+    loss: "l2", "huber" (tuning 1.345) or "bisquare" (4.685); tuning: the loss's constant in units of the scale.
+    scale: the residuals' standard deviation in seconds; None estimates it per call and iteration as 1.4826 x the exact median
+    of |r| over the used channels.  warmup: iterations of plain weighted least squares before the robust weights start (the
+    first guess may be kilometres off, and the median residual with it).
+    Iteration j at n: r = Ti - (n[3] + R / c0); q = 1 for "l2", for j < warmup and where the scale s is not > 0 (a noise-free
+    call); otherwise with u = |r| / (tuning s): huber q = 1 (u <= 1), 1 / u; bisquare q = (1 - u^2)^2 (u < 1), 0.
+    w = weights q; dn = (sum w g g^T + 1e-5 I)^-1 sum w g r; n += 0.7 dn for j < 4, dn after.
+
+    Returns n [ncalls x 4]; a call without a used channel is a NaN row.  With return_stats also a dict, per call, from one
+    more pass at n with q formed as for j >= warmup:
+      history        [ncalls x Nbiter x 4]  the iterate after every iteration
+      scale          [ncalls]               s; NaN where no q was formed ("l2", no used channel)
+      robust_weights [ncalls x channel]     q; NaN on unused channels
+      residuals      [ncalls x channel]     r; NaN on unused channels
+      nused          [ncalls]               used channels
+      weight_sum     [ncalls]               sum of w
+      variance       [ncalls]               sum w r^2 / (nused - p), p = 3 with fix_z else 4; NaN where nused <= p
+      covariance     [ncalls x p x p]       variance inv(G^T W G), solve_lq_batch's rule (regularised where cond > 1 / eps), on the host
+      uncertainty    [ncalls x p]           sqrt of the covariance's diagonal
+    Every sum has a fixed order and the median is exact integer work: run-to-run bit-identical and independent of the other
+    calls of the batch.  With loss="l2" and weights=None, n and history equal solve_lq_batch's bit for bit.  Limits:
+    robust_limits().  A bad argument raises ValueError on the host before any device work.  Containers as solve_lq_batch."""
+    nch, ncalls, code, tuning, scale, Nbiter, warmup, per_call = _robust_check(Ti, cable_pos, c0, weights, loss, tuning, scale, Nbiter,
+                                                                               warmup, first_guess)
+    given = (Ti, cable_pos, weights, first_guess)
+    cable = _cable(cable_pos, _device_of(*given))
+    d = cable.device
+    t = _f64(Ti, d)
+    w = _f64(weights, d) if weights is not None else None
+    fg = None
+    if first_guess is not None:
+        fg = _f64(first_guess, d)
+        if fg.dim() == 1:
+            fg = fg.reshape(1, -1).expand(ncalls, -1).contiguous()
+    p = 3 if fix_z else 4
+    lib = _lib.lib
+    with torch.cuda.device(d):
+        hist = torch.empty((ncalls, Nbiter, 4), dtype=torch.float64, device=d)
+        n = torch.empty((ncalls, 4), dtype=torch.float64, device=d)
+        gtg = torch.empty((ncalls, p, p), dtype=torch.float64, device=d)
+        ssr, wsum, sc = (torch.empty((ncalls,), dtype=torch.float64, device=d) for _ in range(3))
+        nused = torch.empty((ncalls,), dtype=torch.int32, device=d)
+        q = torch.empty((ncalls, nch), dtype=torch.float64, device=d) if return_stats else None
+        r = torch.empty((ncalls, nch), dtype=torch.float64, device=d) if return_stats else None
+        nbytes = ctypes.c_size_t()
+        _lib.check(lib.d4w_loc_robust_ws_bytes(nch, ncalls, ctypes.byref(nbytes)))
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=d) if nbytes.value else None
+        if ncalls:                               # (an empty tensor has no pointer to hand over)
+            _lib.check(lib.d4w_loc_robust_f64(dev.ptr(cable), nch, dev.ptr(t), ncalls, dev.ptr(w) if w is not None else None, int(per_call),
+                                              float(c0), Nbiter, warmup, int(bool(fix_z)), code, tuning, scale,
+                                              dev.ptr(fg) if fg is not None else None, dev.out_ptr(hist) if Nbiter else None, dev.out_ptr(n),
+                                              dev.out_ptr(gtg), dev.out_ptr(ssr), dev.out_ptr(wsum), dev.out_ptr(nused), dev.out_ptr(sc),
+                                              dev.out_ptr(q) if q is not None else None, dev.out_ptr(r) if r is not None else None,
+                                              dev.out_ptr(ws) if ws is not None else None, dev.stream_ptr(t)))
+    if not return_stats:
+        return _back(n, *given)
+    cnt = nused.cpu().numpy().astype(np.int64)
+    with np.errstate(all="ignore"):
+        var = np.where(cnt > p, ssr.cpu().numpy() / np.maximum(cnt - p, 1), np.nan)
+        cov = _covariance(np.where((cnt > 0)[:, None, None], gtg.cpu().numpy(), np.nan), var, quiet=True)
+        unc = np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
+    stats = {"variance": var, "covariance": cov, "uncertainty": unc, "nused": cnt}
+    stats = {k: _back(torch.from_numpy(np.ascontiguousarray(v)).to(d), *given) for k, v in stats.items()}
+    stats.update({k: _back(v, *given) for k, v in (("history", hist), ("scale", sc), ("robust_weights", q), ("residuals", r),
+                                                    ("weight_sum", wsum))})
+    return _back(n, *given), stats
+
+
+def relocate(trace, fs, cable_pos, c0, n, length, max_lag, lead=0, rounds=1, order=3, loss="huber", tuning=None, coef_power=2.0,
+             min_coef=0.0, Nbiter=10, fix_z=True, weights=None, next_block=None, return_stats=False):
+    """The adaptive-stacking loop of refine_arrivals' docstring as one call: located calls n [ncalls x 4] = [x, y, z, t0]
+    (solve_lq_batch's result) are beamformed, every channel is re-picked against the beam, and the position is solved again
+    with the correlation coefficients as weights and a robust loss.  A composition of the package's own calls on the callers'
+    device and stream; per round
+        start = round(n[:, 3] fs) - lead                                                     (int64, half to even)
+        beam, _ = beamform(trace, fs, cable_pos, c0, n[:, :3], start, length, order, weights, next_block=next_block)
+        Ti, coef = refine_arrivals(trace, fs, cable_pos, c0, n[:, :3], beam, start, max_lag, min_coef, weights, next_block)
+        n = solve_robust_batch(Ti, cable_pos, c0, weights=max(coef, 0) ** coef_power, loss=loss, tuning=tuning, Nbiter=Nbiter,
+                               warmup=0, fix_z=fix_z, first_guess=n)
+    in float64 for the weights.  coef_power = 0 means unit weights on the channels that have an arrival.  warmup is 0: n is a
+    located call, not the default guess.  lead: samples of the beam before the emission sample, so that the template holds
+    the call's onset; length: samples of the beam (the call's length + 2 lead).  max_lag: see refine_arrivals -- under half the
+    dominant period; the robust loss takes the edge off a cycle skip on a minority of channels, it does not repair a majority.
+    weights: float32 [channel] for the beam and the alignment (dead channels: 0).  A NaN row of n (a call without a pick) stays
+    a NaN row.  Returns n [ncalls x 4]; with return_stats also a dict of the last round's solver stats (solve_robust_batch)
+    and its Ti, coef and beam.  A CUDA float32 trace is read in place every round; a NumPy trace is uploaded by every call."""
+    rounds = _whole(rounds, "rounds", 1)
+    lead = _whole(lead, "lead", 0)
+    if isinstance(coef_power, bool) or _shape(coef_power) != () or not np.isfinite(coef_power) or coef_power < 0:
+        raise ValueError("coef_power must be a finite number >= 0, got %r" % (coef_power,))
+    if _shape(n)[1:] != (4,) or len(_shape(n)) != 2:
+        raise ValueError("n must be [ncalls x 4] = [x, y, z, t0] per call, got %s" % (_shape(n),))
+    if not isinstance(loss, str) or loss not in _LOSSES:
+        raise ValueError("loss must be one of %s, got %r" % (sorted(_LOSSES), loss))
+    stats = Ti = coef = beam = None
+    for _ in range(rounds):
+        if dev.is_tensor(n):
+            start = torch.nan_to_num(torch.round(n[:, 3].to(torch.float64) * fs), nan=0.0).to(torch.int64) - lead
+            pos = n[:, :3]
+        else:
+            n = np.asarray(n, dtype=np.float64)
+            start = np.nan_to_num(np.round(n[:, 3] * fs), nan=0.0).astype(np.int64) - lead
+            pos = n[:, :3]
+        beam, _t = beamform(trace, fs, cable_pos, c0, pos, start=start, length=length, order=order, weights=weights, next_block=next_block)
+        Ti, coef = refine_arrivals(trace, fs, cable_pos, c0, pos, beam, start, max_lag, min_coef=min_coef, weights=weights,
+                                   next_block=next_block)
+        if dev.is_tensor(coef):
+            w = torch.clamp(coef.to(torch.float64), min=0.0) ** float(coef_power)
+        else:
+            w = np.maximum(coef.astype(np.float64), 0.0) ** float(coef_power)
+        out = solve_robust_batch(Ti, cable_pos, c0, weights=w, loss=loss, tuning=tuning, Nbiter=Nbiter, warmup=0, fix_z=fix_z,
+                                 first_guess=n, return_stats=return_stats)
+        n, stats = out if return_stats else (out, None)
+    if not return_stats:
+        return n
+    stats.update(Ti=Ti, coef=coef, beam=beam)
+    return n, stats

@@ -951,6 +951,44 @@ int d4w_align_f32(const float* x, int64_t pitch, int nch, int ns, const float* x
                   const float* weights /* or NULL */, double fs, double min_coef, int subsample, double* Ti, float* coef,
                   int32_t* lag /* or NULL */, float* rho /* or NULL */, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Robust weighted relocation (das4whales_amd/csrc/robust.hip): d4w_loc_solve_f64's damped Gauss-Newton with per-channel
+ * weights and an iteratively reweighted robust loss, the second solve after d4w_align_f32 (the reference has none).
+ * float64; every pointer is DEVICE memory; cable_pos, Ti, first_guess, history, n_out, gtg as for d4w_loc_solve_f64.
+ *
+ *   weights: NULL (ones), [nch] (weights_per_call = 0) or [ncalls][nch] (weights_per_call != 0).  Channel ch of call c is
+ *     USED iff Ti[c][ch] is not NaN and its weight is > 0: a NaN, zero or negative weight means "not used".  The Ti and the
+ *     cable row of an unused channel may hold anything and change no bit of any result.
+ *   loss: 0 = l2, 1 = Huber, 2 = Tukey's bisquare; tuning > 0 (1.345 and 4.685 are the usual values).
+ *   Iteration j = 0 .. nbiter - 1 at the iterate n, rows g and distance R as d4w_loc_solve_f64: r = Ti - (n3 + R / c0);
+ *     q = 1 when loss = 0 or j < warmup; otherwise s = scale if scale > 0, else 1.4826 x the exact median of |r| over the
+ *     used channels (an even count: (a + b) * 0.5 of the two middle order statistics); if s is not > 0 every q = 1; else with
+ *     u = |r| / (tuning s):  Huber q = 1 for u <= 1, else 1 / u;  bisquare q = (1 - u^2)^2 for u < 1, else 0.
+ *     w = weight q;  A = sum w g g^T + 1e-5 I;  b = sum w g r;  dn = A^-1 b (Cholesky);  n += 0.7 dn for j < 4, dn after.
+ *   Final pass at n_out, with q as an iteration j >= warmup forms it: gtg [ncalls][p][p] = sum w g g^T without the 1e-5,
+ *     ssr [ncalls] = sum w r^2, wsum [ncalls] = sum w, nused [ncalls] int32 = used channels, scale_out [ncalls] = s (NaN
+ *     where no q was formed: loss = 0, or no used channel), robust_weights and residuals [ncalls][nch] = q and r per channel
+ *     (NaN on unused channels).  wsum, scale_out, robust_weights and residuals each or NULL.
+ *   A call without a used channel gives NaN rows in history and n_out, zeros in gtg, ssr, wsum and nused.
+ *   Every sum has a fixed order and the median is integer work: run-to-run bit-identical, independent of the other calls.
+ *   With loss = 0 and weights = NULL, history, n_out, gtg, ssr and nused equal d4w_loc_solve_f64's bit for bit.
+ *
+ * d4w_loc_robust_limits: resident_channels = the largest nch whose |r| stay in LDS for the median (above it they go through
+ *   the workspace), digit_bits = the bits one pass of the radix select resolves.
+ * d4w_loc_robust_ws_bytes: bytes of DEVICE scratch d4w_loc_robust_f64 needs for (nch, ncalls): 0 up to resident_channels.
+ *   ws may be NULL where that is 0, and with loss = 0 or a given scale (no median is taken).
+ * Errors: D4W_EINVAL for a NULL required pointer, nch < 1, ncalls < 0, c0 or tuning not positive and finite, nbiter outside
+ *   0 .. 100000, nbiter > 0 without history, warmup < 0, loss outside 0 .. 2, scale neither 0 nor positive and finite,
+ *   weights_per_call without weights, a missing workspace.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_loc_robust_limits(int* resident_channels, int* digit_bits);
+int d4w_loc_robust_ws_bytes(int nch, int ncalls, size_t* bytes);
+int d4w_loc_robust_f64(const double* cable_pos, int nch, const double* Ti, int ncalls, const double* weights /* or NULL */,
+                       int weights_per_call, double c0, int nbiter, int warmup, int fix_z, int loss, double tuning,
+                       double scale /* 0: estimate */, const double* first_guess /* or NULL */, double* history, double* n_out,
+                       double* gtg, double* ssr, double* wsum /* or NULL */, int* nused, double* scale_out /* or NULL */,
+                       double* robust_weights /* or NULL */, double* residuals /* or NULL */, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
