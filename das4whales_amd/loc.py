@@ -8,7 +8,10 @@ the [ncalls x channel] arrival times these take; `delay_table`, `stack_grid`, `s
 `beamform` (csrc/beam.hip) close the chain with the waveform of a located call, the strain of all channels advanced by their
 travel times from the position and summed; `refine_arrivals` (csrc/align.hip) correlates every channel with that waveform
 around the predicted moveout and returns sub-sample arrival times for a second solve; `solve_robust_batch` (csrc/robust.hip) is
-that solve, with per-channel weights and a robust loss, and `relocate` the loop beam -> re-pick -> relocate as one call.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
+that solve, with per-channel weights and a robust loss, and `relocate` the loop beam -> re-pick -> relocate as one call;
+`received_levels` (csrc/levels.hip) says how loud a located call is on every channel -- the mean square of the strain in a
+window that follows the moveout, the mean square of a noise window before it, the peak --, `levels_db` turns that into a level
+and an SNR in dB and `fit_spreading` fits the level against range.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
 same device and stream.  The four small per-channel helpers (distances, radii, angles) are host float64 arithmetic for NumPy input, like the
 index arithmetic of the other namespaces; for tensors they stay on the device.
 
@@ -1191,3 +1194,153 @@ def relocate(trace, fs, cable_pos, c0, n, length, max_lag, lead=0, rounds=1, ord
         return n
     stats.update(Ti=Ti, coef=coef, beam=beam)
     return n, stats
+
+
+# ------------------------------------------------------------------------------------------
+# beyond the reference: received level and SNR of located calls per channel (csrc/levels.hip), and a spreading-loss fit
+# ------------------------------------------------------------------------------------------
+def level_limits():
+    """(largest number of calls, largest length -- of the signal window, and of noise_length + gap --, channels per workgroup)
+    of the level kernel."""
+    a, b, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib.d4w_level_limits(ctypes.byref(a), ctypes.byref(b), ctypes.byref(w)))
+    return a.value, b.value, w.value
+
+
+def _level_check(a, start, length, noise_length, gap, delays):
+    """The arguments only received_levels has against the shared ones, on the host before any device work: (L, N, gap)."""
+    max_calls, max_length, _ = level_limits()
+    if a.ncalls > max_calls:
+        raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, max_calls))
+    ss = _shape(start)
+    if ss not in ((), (a.ncalls,)) or _dtype_name(start)[:3] not in ("int", "uin"):
+        raise ValueError("start must be an int or [ncalls] = (%d,) ints, got shape %s of %s" % (a.ncalls, ss, _dtype_name(start)))
+    L = _whole(length, "length", 1, max_length)
+    N = _whole(noise_length, "noise_length", 0, max_length)
+    gap = _whole(gap, "gap", 0, max_length)
+    if N + gap > max_length:
+        raise ValueError("noise_length + gap = %d is more than the %d one launch takes" % (N + gap, max_length))
+    if delays is not None and (_shape(delays) != (a.ncalls, a.nch) or _dtype_name(delays) != "int32"):
+        raise ValueError("delays must be int32 [ncalls x channel] = %s (beam_delays(rounded=True)), got %s %s"
+                         % ((a.ncalls, a.nch), _dtype_name(delays), _shape(delays)))
+    return L, N, gap
+
+
+def received_levels(trace, fs, cable_pos, c0, pos, start, length, noise_length=0, gap=0, weights=None, next_block=None, *, delays=None):
+    """How loud located calls are on every channel: the mean square of the strain in a window that follows the call's travel
+    time, the mean square in a noise window just before the call arrives, and the largest sample of the signal window.  With
+    n0 = start[c] + r[c, ch], r = beam_delays(rounded=True):
+        signal[c, ch] = mean of trace[ch, n0 + j]^2                      over 0 <= j < length
+        noise[c, ch]  = mean of trace[ch, n0 - gap - noise_length + j]^2 over 0 <= j < noise_length
+        peak[c, ch]   = max of |trace[ch, n0 + j]|                       over 0 <= j < length       (exact)
+    Returns (signal, noise, peak), float32 [ncalls x channel].  A window gives a value only if it lies wholly inside the record,
+    NaN otherwise; noise_length = 0 means no noise window (noise is all NaN).  A NaN sample makes its window's mean square NaN,
+    and peak is NaN wherever signal is.  levels_db turns the pair into a level and an SNR in dB, fit_spreading fits the
+    level against range.
+
+    trace, weights, next_block, start, pos: as for beamform and refine_arrivals (a CUDA float32 view with unit column stride is
+    read in place; start an int or [ncalls] ints, e.g. round(t0 fs) - lead; next_block continues the record).  weights is a
+    mask here: a channel of weight 0 is never read and its three values are NaN, a non-zero weight scales nothing.
+    length, noise_length, gap: whole numbers of samples, length >= 1, the others >= 0.  gap keeps the noise window clear of
+    the call's onset.  delays: beam_delays(rounded=True) for these positions, built here when None.  Limits: level_limits().
+    To level a band, band-limit trace first (dsp.bp_filt).
+    The sums are float32 in an order that depends on the window length alone (64 interleaved chains, added pairwise): run-to-run
+    bit-identical, independent of the other calls of the batch, of the alignment of a window and of where next_block begins;
+    a scaling of trace by 2^k scales signal and noise by 4^k and peak by 2^k exactly.  A bad argument raises ValueError on the
+    host before any device work.  NumPy in -> NumPy out; any tensor in -> tensors on that device and stream."""
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights)
+    L, N, gap = _level_check(a, start, length, noise_length, gap, delays)
+    _upload(a, like=(start, delays))
+    d = a.device
+    if dev.is_tensor(start):
+        s = start.to(d, torch.int64).reshape(-1)
+    else:
+        s = torch.from_numpy(np.array(start, dtype=np.int64).reshape(-1)).to(d)
+    s = s.expand(a.ncalls).contiguous()
+    with torch.cuda.device(d):
+        signal, noise, peak = (torch.empty((a.ncalls, a.nch), dtype=torch.float32, device=d) for _ in range(3))
+        if a.ncalls:
+            r = _beam_delays(a, True) if delays is None else _given_table(delays, d)
+            nb, w = a.nb, a.w
+            _lib.check(_lib.lib.d4w_level_f32(dev.ptr(a.e), a.pitch, a.nch, a.ns, dev.ptr(nb) if nb is not None else None, a.pitch_nb,
+                                              nb.shape[1] if nb is not None else 0, dev.ptr(r), dev.ptr(s), a.ncalls, L, gap, N,
+                                              dev.ptr(w) if w is not None else None, dev.out_ptr(signal), dev.out_ptr(noise),
+                                              dev.out_ptr(peak), dev.stream_ptr(a.e)))
+    return tuple(_out(y, a.as_tensor) for y in (signal, noise, peak))
+
+
+def levels_db(signal, noise=None):
+    """received_levels' mean squares in decibels, float64: level_db = 10 log10(signal), and with noise given
+    (level_db, snr_db) with snr_db = 10 log10(signal / noise).  IEEE results without warnings: signal 0 gives -inf, noise 0
+    gives +inf, 0 / 0 and every NaN give NaN.  On strain the level is relative (dB re 1 strain^2), not a pressure level.
+    Small arithmetic on the container it was given: NumPy in -> NumPy out; a tensor in -> tensors on its device."""
+    d = _device_of(signal, noise)
+    if d is not None:
+        s = (signal if dev.is_tensor(signal) else torch.from_numpy(np.asarray(signal))).to(d, torch.float64)
+        level = 10.0 * torch.log10(s)
+        if noise is None:
+            return level
+        q = (noise if dev.is_tensor(noise) else torch.from_numpy(np.asarray(noise))).to(d, torch.float64)
+        return level, 10.0 * torch.log10(s / q)
+    # on the host a tensor goes through the NumPy expressions as well: one result for one input, whatever the container
+    back = (lambda v: torch.from_numpy(v)) if dev.is_tensor(signal) or dev.is_tensor(noise) else (lambda v: v)
+    s = np.asarray(signal.numpy() if dev.is_tensor(signal) else signal, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        level = np.asarray(10.0 * np.log10(s))
+        if noise is None:
+            return back(level)
+        q = np.asarray(noise.numpy() if dev.is_tensor(noise) else noise, dtype=np.float64)
+        return back(level), back(np.asarray(10.0 * np.log10(s / q)))
+
+
+def fit_spreading(level_db, cable_pos, pos, snr_db=None, min_snr_db=None):
+    """A spreading law through the levels of every call, by ordinary least squares per call:
+        level_db[c, ch] = SL[c] - k[c] 10 log10(range[c, ch] / 1 m),        range = |cable_pos[ch] - pos[c]|
+    over the channels whose level is finite and, when both snr_db and min_snr_db are given, whose snr_db >= min_snr_db.
+    Returns (SL [ncalls] float64, k [ncalls] float64, used [ncalls] int32 = the channels of the fit); SL and k are NaN where
+    fewer than two channels remain or all their ranges are equal.  k = 2 for an amplitude that falls as 1 / r (spherical
+    spreading), 1 for cylindrical.  On strain SL is a relative level -- the level_db the law gives at 1 m -- and not a source
+    level in dB re 1 uPa: nothing here calibrates strain to pressure.
+    level_db: [ncalls x channel] (or [channel] for one call), what levels_db returns; pos: [ncalls x 3] or [3].
+    Float64, closed form (the two sums of a straight-line fit about the means); small arithmetic on the container level_db
+    came in, not a kernel: NumPy in -> NumPy out; a tensor in -> tensors on its device."""
+    nch = _channels(cable_pos)
+    ncalls = _npos(pos)
+    ls = _shape(level_db)
+    if ls not in ((ncalls, nch),) + (((nch,),) if ncalls == 1 else ()):
+        raise ValueError("level_db must be [ncalls x channel] = %s, got %s" % ((ncalls, nch), ls))
+    if snr_db is not None and _shape(snr_db) != ls:
+        raise ValueError("snr_db must have level_db's shape %s, got %s" % (ls, _shape(snr_db)))
+    if min_snr_db is not None and (isinstance(min_snr_db, bool) or _shape(min_snr_db) != () or np.isnan(min_snr_db)):
+        raise ValueError("min_snr_db must be None or a number, got %r" % (min_snr_db,))
+    as_tensor = dev.is_tensor(level_db)
+    d = level_db.device if as_tensor else "cpu"
+
+    def t64(v):
+        v = v if dev.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(np.asarray(v, dtype=np.float64)))
+        return v.to(d, torch.float64)
+
+    y = t64(level_db).reshape(ncalls, nch)
+    p = t64(pos).reshape(ncalls, 3)
+    diff = t64(cable_pos)[None, :, :] - p[:, None, :]
+    u = 10.0 * torch.log10(torch.sqrt((diff * diff).sum(-1)))
+    ok = torch.isfinite(y) & torch.isfinite(u)
+    if snr_db is not None and min_snr_db is not None:
+        ok &= t64(snr_db).reshape(ncalls, nch) >= float(min_snr_db)
+    used = ok.sum(1)
+    n = used.to(torch.float64)
+    zero = torch.zeros((), dtype=torch.float64, device=y.device)
+    um = torch.where(ok, u, zero).sum(1) / n
+    ym = torch.where(ok, y, zero).sum(1) / n
+    du = torch.where(ok, u - um[:, None], zero)
+    suu = (du * du).sum(1)
+    suy = (du * torch.where(ok, y - ym[:, None], zero)).sum(1)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=y.device)
+    inf = torch.full((), float("inf"), dtype=torch.float64, device=y.device)
+    fit = (used >= 2) & (torch.where(ok, u, -inf).amax(1) > torch.where(ok, u, inf).amin(1))      # two channels, two ranges
+    k = torch.where(fit, -suy / suu, nan)
+    SL = torch.where(fit, ym + k * um, nan)
+    used = used.to(torch.int32)
+    if as_tensor:
+        return SL, k, used
+    return SL.numpy(), k.numpy(), used.numpy()

@@ -989,6 +989,37 @@ int d4w_loc_robust_f64(const double* cable_pos, int nch, const double* Ti, int n
                        double* gtg, double* ssr, double* wsum /* or NULL */, int* nused, double* scale_out /* or NULL */,
                        double* robust_weights /* or NULL */, double* residuals /* or NULL */, void* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Received level of located calls per channel (das4whales_amd/csrc/levels.hip; the reference has none of
+ * this): the mean square of the strain in a window that follows the call's moveout, the mean square in a noise window just
+ * before it, and the largest sample of the signal window.  Every pointer is DEVICE memory unless it returns a limit.
+ *
+ *   x, pitch, nch, ns, xnext, pitch_next, ns_next, r, start, weights: as for d4w_align_f32 (r [ncalls][nch] int32 rounded
+ *     delays, start [ncalls] int64 clamped to +-2^62; the record is ns + ns_next samples long).
+ *   n0 = start[c] + r[c][ch];  signal window [n0, n0 + length);  noise window [n0 - gap - noise_length, n0 - gap).
+ *   A window is valid iff it lies wholly inside the record; noise_length = 0 means no noise window.
+ *     signal[c][ch] = (sum of x^2 over the signal window) / (float)length
+ *     noise[c][ch]  = (sum of x^2 over the noise window) / (float)noise_length
+ *     peak[c][ch]   = max |x| over the signal window (exact)
+ *   float32; the sums are 64 interleaved chains (chain i takes the terms i, i + 64, ... in increasing order, one fmaf each
+ *   from 0) added pairwise at distances 32, 16, 8, 4, 2, 1: an order that depends on the window length alone.
+ *   An invalid window gives NaN; a NaN sample makes its window's mean square NaN; peak is NaN wherever signal is.  A channel
+ *   of weight 0 is not read at all and its three outputs are NaN; a non-zero weight scales nothing.
+ *
+ * d4w_level_limits: the largest ncalls (65535), the largest length and noise_length + gap (2^30), and the channels one
+ *   workgroup takes (4; what the tests size their shapes by).
+ * d4w_level_f32: signal, noise, peak [ncalls][nch] float32; noise may be NULL iff noise_length = 0 (given, it is all NaN
+ *   then).  ncalls = 0 launches nothing.  One wave per four channels of a call, no LDS, no atomics, no workspace.
+ * Errors: D4W_EINVAL for a NULL required pointer (with ncalls > 0), nch or ns < 1, ncalls < 0 or beyond the limit,
+ *   length < 1, noise_length < 0, gap < 0, length or noise_length + gap beyond the limit, pitch < ns, xnext with
+ *   ns_next < 1 or pitch_next < ns_next, ns_next != 0 without xnext, noise = NULL with noise_length > 0.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_level_limits(int* max_calls, int* max_length, int* channels);
+int d4w_level_f32(const float* x, int64_t pitch, int nch, int ns, const float* xnext /* or NULL */, int64_t pitch_next, int ns_next,
+                  const int32_t* r, const int64_t* start, int ncalls, int length, int gap, int noise_length,
+                  const float* weights /* or NULL */, float* signal, float* noise /* or NULL iff noise_length == 0 */, float* peak,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
