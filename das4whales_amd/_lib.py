@@ -232,6 +232,12 @@ def _load():
         "d4w_level_limits": (c_int, [P(c_int), P(c_int), P(c_int)]),
         "d4w_level_f32": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_int,
                                   c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "d4w_project_limits": (c_int, [P(c_int), P(c_int), P(c_int)]),
+        "d4w_project_f32": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "d4w_project_subtract_f32": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p,
+                                             ctypes.c_int64, c_void_p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch: fail loudly

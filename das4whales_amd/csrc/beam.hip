@@ -38,7 +38,7 @@
 //   2 ncalls nt ceil(nch / 128) words of partials written and read back (under 2 % of the reads).  Measured with segments
 //   of 256 / 128 / 64 channels at 11 020 x 12 000: one call of order 0 takes 0.60 / 0.38 / 0.30 ms (two, four or eight
 //   workgroups per compute unit), 64 calls 4.90 / 4.94 / 5.35 ms, and the workspace of 64 calls is 0.27 / 0.54 / 1.06 GB.
-#include "moveout.h"
+#include "taps.h"
 
 #ifndef D4W_EMU
 #pragma clang fp contract(off)
@@ -105,21 +105,8 @@ __global__ __launch_bounds__(kBeamThreads) void beam_sum(const float* __restrict
         const long long lo = q0 + kLo, hi = q0 + (kBeamTile - 1) + kHi;
         if (hi < 0 || lo >= ntot) continue;                  // the whole span lies outside the record
 
-        float l[kTaps];                                      // weight x interpolation coefficient
-        if constexpr (ORDER == 0) {
-            l[0] = w;
-        } else if constexpr (ORDER == 1) {
-            const float f = fr[e];
-            l[0] = w * (1.f - f);
-            l[1] = w * f;
-        } else {
-            const float f = fr[e];
-            const float fp = f + 1.f, fm = f - 1.f, fmm = f - 2.f;
-            l[0] = w * (-(f * fm * fmm) * (1.f / 6.f));
-            l[1] = w * ((fp * fm * fmm) * 0.5f);
-            l[2] = w * (-(fp * f * fmm) * 0.5f);
-            l[3] = w * ((fp * f * fm) * (1.f / 6.f));
-        }
+        float l[kTaps];                                      // weight x interpolation coefficient (taps.h)
+        delay_taps<ORDER>(w, ORDER == 0 ? 0.f : fr[e], l);
 
         // the terms of this channel on a row pointer p = &row[q0]: every tap lies inside that block
         auto plain = [&](const float* __restrict__ p) {

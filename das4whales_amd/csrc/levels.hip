@@ -40,7 +40,7 @@
 //   L = N = 400 (2.26 GB): 0.339 ms, 6.7 TB/s, against 0.368 + 0.037 ms for the order-0 beam over the same samples; with 1, 2,
 //   8 or 16 channels per wave instead of 4 (the same sum order) the call took 0.545, 0.401, 0.457, 0.580 ms against 0.382
 //   (profiles/levels/).
-#include "moveout.h"
+#include "taps.h"
 
 #ifndef D4W_EMU
 #pragma clang fp contract(off)
@@ -56,28 +56,7 @@ constexpr int kLevelMaxCalls = 65535;                        // grid limit
 constexpr int kLevelMaxLength = 1 << 30;                     // of L and of N + gap
 constexpr long long kLevelStartMax = 1ll << 62;              // start is clamped here: the sums below cannot overflow
 
-// a window of len samples: sample i is pa[i] for i < split, pb[i - split] after; len = 0: not valid, never read
-struct LevelWindow {
-    const float* pa;
-    const float* pb;
-    int split, len;
-};
-
-// the window [q0, q0 + len) of a row (row / rown: the block's and the next block's), valid iff it lies inside the record
-__device__ __forceinline__ LevelWindow level_window(const float* row, const float* rown, long long q0, int len, long long ns, long long ntot) {
-    LevelWindow w{nullptr, nullptr, 0, 0};
-    if (len < 1 || q0 < 0 || q0 + len > ntot) return w;
-    w.len = len;
-    if (q0 >= ns) {
-        w.pa = rown + (q0 - ns);
-        w.split = len;
-    } else {
-        w.pa = row + q0;
-        w.pb = rown;
-        w.split = (int)min((long long)len, ns - q0);
-    }
-    return w;
-}
+// LevelWindow, level_window: taps.h (project.hip describes its windows the same way)
 
 // one trip of a lane: the terms i = j + 16 s, s < 4, of its four chains (j = the lane's place among the 16 of its channel + 64 k)
 template <bool SEAM>

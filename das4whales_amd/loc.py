@@ -11,7 +11,10 @@ around the predicted moveout and returns sub-sample arrival times for a second s
 that solve, with per-channel weights and a robust loss, and `relocate` the loop beam -> re-pick -> relocate as one call;
 `received_levels` (csrc/levels.hip) says how loud a located call is on every channel -- the mean square of the strain in a
 window that follows the moveout, the mean square of a noise window before it, the peak --, `levels_db` turns that into a level
-and an SNR in dB and `fit_spreading` fits the level against range.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
+and an SNR in dB and `fit_spreading` fits the level against range; `project_calls`, `subtract_calls` and `remove_calls`
+(csrc/project.hip) are the transpose of the beam: the call's waveform laid back on every channel along its moveout, fitted
+(a signed least-squares amplitude and a correlation coefficient per channel) and subtracted, so that a second pass over the
+residual sees the weaker call underneath.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
 same device and stream.  The four small per-channel helpers (distances, radii, angles) are host float64 arithmetic for NumPy input, like the
 index arithmetic of the other namespaces; for tensors they stay on the device.
 
@@ -1344,3 +1347,190 @@ def fit_spreading(level_db, cable_pos, pos, snr_db=None, min_snr_db=None):
     if as_tensor:
         return SL, k, used
     return SL.numpy(), k.numpy(), used.numpy()
+
+
+# ------------------------------------------------------------------------------------------
+# beyond the reference: the transpose of the beam -- located calls projected onto the channels and subtracted (csrc/project.hip)
+# ------------------------------------------------------------------------------------------
+def project_limits():
+    """(largest number of calls, largest beam length, channels per workgroup of the fit) of the projection kernels."""
+    a, b, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib.d4w_project_limits(ctypes.byref(a), ctypes.byref(b), ctypes.byref(w)))
+    return a.value, b.value, w.value
+
+
+def _project_check(a, beam, start, order, delays, amp=_SKIP):
+    """The arguments only project_calls and subtract_calls have against the shared ones, on the host before any device work:
+    (L, the given delay tables as a tuple)."""
+    max_calls, max_length, _ = project_limits()
+    if a.ncalls > max_calls:
+        raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, max_calls))
+    bs = _shape(beam)
+    if not ((len(bs) == 2 and bs[0] == a.ncalls) or (len(bs) == 1 and a.ncalls == 1)) or _dtype_name(beam) != "float32":
+        raise ValueError("beam must be float32 [ncalls x L] = (%d, L) (or [L] for one call), got %s %s" % (a.ncalls, _dtype_name(beam), bs))
+    if bs[-1] < 1 or bs[-1] > max_length:
+        raise ValueError("the beam length %d is outside 1 .. %d" % (bs[-1], max_length))
+    if amp is not _SKIP:
+        if _shape(amp) not in ((a.ncalls, a.nch),) + (((a.nch,),) if a.ncalls == 1 else ()) or _dtype_name(amp) != "float32":
+            raise ValueError("amp must be float32 [ncalls x channel] = %s, got %s %s" % ((a.ncalls, a.nch), _dtype_name(amp), _shape(amp)))
+    return _beam_check(a, start, bs[-1], order, delays)
+
+
+def _order(order):
+    if isinstance(order, bool) or order not in (0, 1, 3):
+        raise ValueError("order must be 0, 1 or 3, got %r" % (order,))
+    return int(order)
+
+
+def _starts(start, a):
+    """start as int64 [ncalls] on the device."""
+    if dev.is_tensor(start):
+        s = start.to(a.device, torch.int64).reshape(-1)
+    else:
+        s = torch.from_numpy(np.array(start, dtype=np.int64).reshape(-1)).to(a.device)
+    return s.expand(a.ncalls).contiguous()
+
+
+def _tables(a, order, tables):
+    """(k or r, f or None) on the device: the given tables, or beam_delays' for the positions a.p."""
+    if tables:
+        return _given_table(tables[0], a.device), (_given_table(tables[1], a.device) if order else None)
+    return (_beam_delays(a, True), None) if order == 0 else _beam_delays(a, False)
+
+
+def _project(a, kr, f, b, s, order):
+    """The fit on device tensors: (amp, coef) float32 [ncalls x nch]; no launch without a call."""
+    amp, coef = (torch.empty((a.ncalls, a.nch), dtype=torch.float32, device=a.device) for _ in range(2))
+    if a.ncalls:
+        nb, w = a.nb, a.w
+        _lib.check(_lib.lib.d4w_project_f32(dev.ptr(a.e), a.pitch, a.nch, a.ns, dev.ptr(nb) if nb is not None else None, a.pitch_nb,
+                                            nb.shape[1] if nb is not None else 0, dev.ptr(kr), dev.ptr(f) if f is not None else None, dev.ptr(b),
+                                            b.shape[1], dev.ptr(s), a.ncalls, order, dev.ptr(w) if w is not None else None, dev.out_ptr(amp),
+                                            dev.out_ptr(coef), dev.stream_ptr(a.e)))
+    return amp, coef
+
+
+def _subtract(a, kr, f, b, s, amp, order, inplace):
+    """The subtraction on device tensors: (y, ynext or None); in place y and ynext are a.e and a.nb themselves."""
+    nb = a.nb
+    if inplace:
+        y, yn, py, pyn = a.e, nb, a.pitch, a.pitch_nb
+    else:
+        y = torch.empty((a.nch, a.ns), dtype=torch.float32, device=a.device)
+        yn = torch.empty((a.nch, nb.shape[1]), dtype=torch.float32, device=a.device) if nb is not None else None
+        py, pyn = a.ns, (nb.shape[1] if nb is not None else 0)
+    none = a.ncalls == 0
+    _lib.check(_lib.lib.d4w_project_subtract_f32(dev.ptr(a.e), a.pitch, a.nch, a.ns, dev.ptr(nb) if nb is not None else None, a.pitch_nb,
+                                                 nb.shape[1] if nb is not None else 0, None if none else dev.ptr(kr),
+                                                 dev.ptr(f) if f is not None and not none else None, None if none else dev.ptr(b),
+                                                 b.shape[1], None if none else dev.ptr(s), None if none else dev.ptr(amp), a.ncalls, order,
+                                                 dev.out_ptr(y), py, dev.out_ptr(yn) if yn is not None else None, pyn, dev.stream_ptr(a.e)))
+    return y, yn
+
+
+def project_calls(trace, fs, cable_pos, c0, pos, beam, start, order=1, weights=None, next_block=None, *, delays=None):
+    """The waveform of located calls projected back onto every channel: the transpose of beamform.  The image of call c on
+    channel ch is its beam laid along the call's moveout with the beam's own interpolation taps,
+        g[c, ch](n) = sum_m l_m beam[c, n - q0 - m],        q0 = start[c] + delay[c, ch],  beam = 0 outside 0 <= j < L
+    (l_m: beamform's coefficients of that order with weight 1; support of L + order samples), and the fit over that support is
+        amp[c, ch]  = sum trace g / sum g g                       the least-squares amplitude of the image on the channel
+        coef[c, ch] = sum trace g / sqrt(sum g g  sum trace^2)    the correlation coefficient, refine_arrivals' form
+    Returns (amp, coef), float32 [ncalls x channel].  amp is signed and coherent -- far less biased by noise than
+    received_levels' mean square -- and is what subtract_calls takes; amp is 0 where the image is all zero, coef is 0 where
+    either energy is.  NaN in both where the support does not lie wholly inside the record, where a sample of the window is
+    NaN, and where weights[ch] = 0 (the channel is never read; a non-zero weight scales nothing: weights is a mask).
+    Every fit is against trace as given, independent of the other calls: overlapping calls are not fitted jointly.
+
+    beam: float32 [ncalls x L] (or [L] for one call), e.g. beamform(..., normalize=True)[0] with the same pos, start and order.
+    A normalized beam holds 1 / channels of every channel's own noise, so amp and coef of a channel are biased up by about
+    (noise energy of the channel) / (channels x energy of the beam) -- negligible on a long cable, visible on a few channels.
+    trace, weights, next_block, start, pos, order, delays: as for beamform (a CUDA float32 view with unit column stride is
+    read in place; delays is beam_delays' r for order 0 and (k, f) otherwise, built here when None).  Limits: project_limits().
+    The sums are float32 in an order that depends on L + order alone (64 interleaved chains, added pairwise): run-to-run
+    bit-identical, independent of the batch and of where next_block begins; a scaling of a channel by 2^k scales amp by 2^k
+    exactly and keeps coef's bits.  A bad argument raises ValueError on the host before any device work.
+    NumPy in -> NumPy out; any tensor in -> tensors on that device and stream."""
+    order = _order(order)
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights)
+    L, tables = _project_check(a, beam, start, order, delays)
+    _upload(a, like=(start, beam) + tables)
+    with torch.cuda.device(a.device):
+        out = _project(a, *_tables(a, order, tables), _given_table(beam, a.device).reshape(a.ncalls, L), _starts(start, a), order)
+    return tuple(_out(y, a.as_tensor) for y in out)
+
+
+def _inplace_view(t):
+    return (dev.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
+            and (t.stride(0) >= t.shape[1] or t.shape[0] == 1))
+
+
+def subtract_calls(trace, fs, cable_pos, c0, pos, beam, start, amp, order=1, next_block=None, inplace=False, *, delays=None):
+    """Located calls taken out of the block, the CLEAN step of array processing:
+        residual = trace, then for c = 0, 1, ... in increasing order: residual[ch, n] -= amp[c, ch] g[c, ch](n)
+    over the support of the image g (project_calls), one fmaf per sample and call, wherever amp[c, ch] is finite and
+    non-zero and the support lies wholly inside the record.  A NaN or zero amp subtracts nothing: mask amp to choose the
+    channels (remove_calls does, by coef).  Returns the residual [channel x time] float32, or (residual, residual_next) when
+    next_block is given (the part of the record past the seam).  A second pass of locate_stack / beamform / refine_arrivals
+    over the residual sees the weaker call the first one hid, and the residual under a call is the noise estimate there.
+
+    inplace=False: new arrays; every sample is written (a copy where no call reaches).  inplace=True: trace (and next_block)
+    must be CUDA float32 tensors with unit column stride -- views into larger buffers are fine --; they are written into and
+    returned, only the samples under a support are touched, and the result has the same bits as out of place.
+    beam, start, order, delays: as for project_calls; amp: float32 [ncalls x channel] (or [channel] for one call).
+    A gather without atomics: run-to-run bit-identical.  A bad argument raises ValueError on the host before any device work.
+    NumPy in -> NumPy out; any tensor in -> tensors on that device and stream."""
+    order = _order(order)
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block)
+    L, tables = _project_check(a, beam, start, order, delays, amp)
+    if inplace and not (_inplace_view(trace) and (next_block is None or (_inplace_view(next_block) and next_block.device == trace.device))):
+        raise ValueError("inplace=True needs trace (and next_block) as CUDA float32 tensors with unit column stride on one device")
+    _upload(a, like=(start, beam, amp) + tables)
+    with torch.cuda.device(a.device):
+        y, yn = _subtract(a, *_tables(a, order, tables), _given_table(beam, a.device).reshape(a.ncalls, L), _starts(start, a),
+                          _given_table(amp, a.device).reshape(a.ncalls, a.nch), order, bool(inplace))
+    if inplace:
+        return trace if next_block is None else (trace, next_block)
+    return _out(y, a.as_tensor) if yn is None else (_out(y, a.as_tensor), _out(yn, a.as_tensor))
+
+
+def remove_calls(trace, fs, cable_pos, c0, pos, start, length, order=1, min_coef=0.0, weights=None, next_block=None, inplace=False,
+                 return_parts=False):
+    """Beam, fit and subtract located calls in one call, with one delay table for the three steps:
+        beam = beamform(trace, ..., start, length, order, weights, normalize=True)
+        amp, coef = project_calls(trace, ..., beam, start, order, weights)
+        amp[coef < min_coef] = NaN                     (min_coef=None masks nothing)
+        residual = subtract_calls(trace, ..., beam, start, amp, order, inplace=inplace)
+    Returns the residual (or (residual, residual_next) with next_block), followed by (beam, amp, coef) when return_parts.
+    The default min_coef = 0 leaves alone the channels where the call's image correlates negatively with the record.
+    Every call is fitted against trace as given and the calls are subtracted in increasing order; two calls that overlap in
+    time on a channel are not fitted jointly, so the louder one belongs first and a second remove_calls over the residual
+    refines the weaker.  The beam holds 1 / channels of every channel's own noise (see project_calls), which this
+    subtracts along with the call.  Arguments as for beamform and subtract_calls; length is the beam's, in samples."""
+    order = _order(order)
+    if min_coef is not None and (isinstance(min_coef, bool) or _shape(min_coef) != () or not np.isfinite(min_coef)):
+        raise ValueError("min_coef must be None or a finite number, got %r" % (min_coef,))
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights)
+    if a.ncalls > project_limits()[0]:
+        raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, project_limits()[0]))
+    L = _whole(length, "length", 1, project_limits()[1])
+    _beam_check(a, start, L, order, None)
+    if inplace and not (_inplace_view(trace) and (next_block is None or (_inplace_view(next_block) and next_block.device == trace.device))):
+        raise ValueError("inplace=True needs trace (and next_block) as CUDA float32 tensors with unit column stride on one device")
+    _upload(a, like=(start,))
+    with torch.cuda.device(a.device):
+        s = _starts(start, a)
+        kr, f = _tables(a, order, ())
+        beam = _beam(a, kr, f, s, L, order, True)
+        amp, coef = _project(a, kr, f, beam, s, order)
+        if min_coef is not None:
+            amp = torch.where(coef < float(min_coef), torch.full((), float("nan"), dtype=torch.float32, device=a.device), amp)
+        y, yn = _subtract(a, kr, f, beam, s, amp, order, bool(inplace))
+    if inplace:
+        res = (trace,) if next_block is None else (trace, next_block)
+    else:
+        res = (_out(y, a.as_tensor),) if yn is None else (_out(y, a.as_tensor), _out(yn, a.as_tensor))
+    res = res[0] if len(res) == 1 else res
+    if not return_parts:
+        return res
+    parts = tuple(_out(t, a.as_tensor) for t in (beam, amp, coef))
+    return (res,) + parts if next_block is None else res + parts

@@ -1020,6 +1020,51 @@ int d4w_level_f32(const float* x, int64_t pitch, int nch, int ns, const float* x
                   const float* weights /* or NULL */, float* signal, float* noise /* or NULL iff noise_length == 0 */, float* peak,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The transpose of the beam: the waveform of a located call projected back onto every channel along its moveout, fitted and
+ * subtracted (das4whales_amd/csrc/project.hip; the reference has none of this).  Every pointer is DEVICE
+ * memory unless it returns a limit.
+ *
+ *   x, pitch, nch, ns, xnext, pitch_next, ns_next, k_or_r, f, start, order: as for d4w_beamform_f32 (the tables of
+ *     d4w_beam_delays: r for order 0, (k, f) for orders 1 and 3; f may be NULL for order 0; start clamped to +-2^62).
+ *   beam [ncalls][length] float32: the waveform of every call, e.g. d4w_beamform_f32's normalized output.
+ *   q0 = start[c] + k_or_r[c][ch];  l_m = the unweighted float32 interpolation coefficients of f[c][ch] (d4w_beamform_f32's
+ *     with weight 1), m = kLo .. kHi = 0 .. 0 / 0 .. 1 / -1 .. 2 for order 0 / 1 / 3.
+ *   image of the beam on the channel, the exact transpose of the beam's taps:
+ *     g[c][ch](n) = sum_m l_m beam[c][n - q0 - m], beam = 0 outside 0 <= j < length; float32, t = l_lo b, then
+ *     t = fmaf(l_m, b, t) in increasing m.  Support n in [q0 + kLo, q0 + length - 1 + kHi], W = length + order samples.
+ *   The window is valid iff the support lies wholly inside the record of ns + ns_next samples.
+ *
+ * d4w_project_limits: the largest ncalls (65535), the largest length (2^30), and the channels one workgroup of the fit
+ *   takes (4; what the tests size their shapes by).
+ * d4w_project_f32: amp, coef [ncalls][nch] float32.  Over the support num = sum x g, den = sum g g, xx = sum x x, each a
+ *   float32 sum in d4w_level_f32's order (term i of the support to chain i mod 64, one fmaf per term from 0, the chains added
+ *   pairwise at distances 32 .. 1): a function of W alone.  amp = num / den (0 where den = 0), coef = num / sqrtf(den xx) (0
+ *   where den or xx is 0).  An invalid window gives NaN in both and is not read; a NaN sample in the window gives NaN in both;
+ *   a channel of weight 0 is not read at all and gives NaN; a non-zero weight scales nothing.  Every fit is against x as
+ *   given, independent of the other calls.  ncalls = 0 launches nothing.  One wave per four channels of a call, the beam
+ *   through 4 KB of LDS, no atomics, no workspace.
+ * d4w_project_subtract_f32: y = x, then for c = 0, 1, ... in increasing order, where amp[c][ch] is finite and non-zero, the
+ *   window is valid and n lies in its support, y[ch][n] = fmaf(-amp[c][ch], g[c][ch](n), y[ch][n]); sample ns + i of the
+ *   record goes to ynext[ch][i].  ynext is given iff xnext is.  A gather: a thread owns its samples and walks the calls; no
+ *   atomics, run-to-run bit-identical, independent of the launch geometry.
+ *   Out of place (y != x; y, ynext must not overlap x, xnext): every sample of y and ynext is written, a copy where no call
+ *   reaches (also with ncalls = 0).  In place (y = x, pitch_y = pitch; ynext = xnext, pitch_ynext = pitch_next): only the
+ *   samples inside a subtracted support are read and stored; ncalls = 0 launches nothing.
+ * Errors: D4W_EINVAL for a NULL required pointer (with ncalls > 0; x and y always), nch or ns < 1, ncalls < 0 or beyond the
+ *   limit, length < 1 or beyond the limit, an order other than 0, 1, 3, f = NULL with order 1 or 3, a pitch below its row,
+ *   xnext with ns_next < 1, ns_next != 0 without xnext, ynext without xnext or the reverse, y = x with another pitch or with
+ *   ynext != xnext, ynext = xnext without y = x, more than 2^31 - 1 (channel, tile of 2048 samples) pairs.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_project_limits(int* max_calls, int* max_length, int* channels);
+int d4w_project_f32(const float* x, int64_t pitch, int nch, int ns, const float* xnext /* or NULL */, int64_t pitch_next, int ns_next,
+                    const int32_t* k_or_r, const float* f /* or NULL for order 0 */, const float* beam, int length, const int64_t* start,
+                    int ncalls, int order, const float* weights /* or NULL */, float* amp, float* coef, void* stream);
+int d4w_project_subtract_f32(const float* x, int64_t pitch, int nch, int ns, const float* xnext /* or NULL */, int64_t pitch_next, int ns_next,
+                             const int32_t* k_or_r, const float* f /* or NULL for order 0 */, const float* beam, int length,
+                             const int64_t* start, const float* amp, int ncalls, int order, float* y, int64_t pitch_y,
+                             float* ynext /* or NULL iff xnext is */, int64_t pitch_ynext, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
