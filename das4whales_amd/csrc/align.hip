@@ -42,7 +42,7 @@
 //   hits across the calls.  The plain form (a wave per channel, a lane per lag, one LDS word per term) was built first and
 //   measured: 1.78 ms for 64 calls at 11 020 channels, L = 400, M = 20, by its count bound by the LDS read rate; this form takes
 //   1.10 ms, its LDS cycles are a sixth and the multiply-adds the same (profiles/align/).
-#include "moveout.h"
+#include "taps.h"
 
 #ifndef D4W_EMU
 #pragma clang fp contract(off)
@@ -58,7 +58,6 @@ constexpr int kAlignPass = kAlignGroup * kAlignRun;          // lags per channel
 constexpr int kAlignMaxCalls = 65535;                        // grid limit
 constexpr int kAlignMaxLength = 4096;                        // 20 s at 200 Hz
 constexpr int kAlignMaxLag = 255;
-constexpr long long kAlignStartMax = 1ll << 62;              // start is clamped here: the sums below cannot overflow
 constexpr int kAlignNone = 0x7fffffff;                       // "no lag yet" in the argmax
 
 static inline int align_row_words(int L, int M) {            // a window row in LDS: every 16-byte read of a pass stays inside it
@@ -87,7 +86,7 @@ __global__ __launch_bounds__(kAlignThreads) void align_pick(const float* __restr
     const int c = blockIdx.y;
     const long long ch0 = (long long)blockIdx.x * kAlignChannels;
     const long long ntot = (long long)ns + (long long)nsn;
-    const long long s0 = min(max(start[c], -kAlignStartMax), kAlignStartMax);
+    const long long s0 = clamp_start(start[c]);
     const float qnan = __int_as_float(0x7fc00000);
 
     const float* __restrict__ t = tmpl + (size_t)c * (size_t)L;
@@ -251,15 +250,9 @@ int d4w_align_f32(const float* x, int64_t pitch, int nch, int ns, const float* x
     if (max_lag < 0 || max_lag > kAlignMaxLag) return fail(D4W_EINVAL, "align: max_lag %d is outside 0 .. %d", max_lag, kAlignMaxLag);
     if (!positive_finite(fs)) return fail(D4W_EINVAL, "align: fs must be positive and finite");
     if (!std::isfinite(min_coef)) return fail(D4W_EINVAL, "align: min_coef must be finite");
-    int rc = check_block("align", nch, ns, pitch);
+    const int rc = check_record("align", nch, ns, pitch, xnext, ns_next, pitch_next);
     if (rc) return rc;
     if (nch > (1 << 30)) return fail(D4W_EINVAL, "align: %d channels, a launch takes 1 .. %d", nch, 1 << 30);
-    if (xnext) {
-        rc = check_block("align, next block", nch, ns_next, pitch_next);
-        if (rc) return rc;
-    } else if (ns_next != 0) {
-        return fail(D4W_EINVAL, "align: %d samples of a next block that is not given", ns_next);
-    }
     const size_t lds = align_lds_bytes(length, max_lag);
     // above 64 KiB a kernel has to opt into its dynamic LDS size; a refused opt-in is this call's error, before any launch
     if (lds > 64 * 1024) D4W_HIP(hipFuncSetAttribute((const void*)align_pick, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -52,7 +52,6 @@ constexpr int kBeamTile = kBeamThreads * kBeamCpt;            // columns per wor
 constexpr int kBeamSegment = 128;                             // channels one thread sums from 0
 constexpr int kBeamMaxCalls = 65535;                          // grid limit
 constexpr int kBeamMaxLength = kMoveoutDelayMax;              // a beam is no longer than the longest delay
-constexpr long long kBeamStartMax = 1ll << 62;                // start is clamped here: the sums below cannot overflow
 
 // grid (ceil(nch / 256), min(ncalls, 65535)); pos [ncalls][3]; k, f, r [ncalls][nch], each or NULL
 __global__ __launch_bounds__(kBeamThreads) void beam_delays(const double* __restrict__ cable, int nch, double inv_c0, double fs,
@@ -86,7 +85,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_sum(const float* __restrict
     constexpr int kTaps = ORDER + 1, kLo = ORDER == 3 ? -1 : 0, kHi = ORDER == 3 ? 2 : ORDER;
     const int tid = threadIdx.x, seg = blockIdx.y, c = blockIdx.z;
     const long long col0 = (long long)blockIdx.x * kBeamTile;
-    const long long b0 = min(max(start[c], -kBeamStartMax), kBeamStartMax) + col0;        // the sample of column col0 at delay 0
+    const long long b0 = clamp_start(start[c]) + col0;        // the sample of column col0 at delay 0
     const long long ntot = (long long)ns + (long long)nsn;
     const int ch0 = seg * kBeamSegment, ch1 = min(nch, ch0 + kBeamSegment);
 
@@ -268,14 +267,8 @@ int d4w_beamform_f32(const float* x, int64_t pitch, int nch, int ns, const float
     if (order != 0 && !f) return fail(D4W_EINVAL, "beamform: order %d needs the fractions f", order);
     int rc = beam_check_shape("beamform", nch, ncalls, length);
     if (rc) return rc;
-    rc = check_block("beamform", nch, ns, pitch);
+    rc = check_record("beamform", nch, ns, pitch, xnext, ns_next, pitch_next);
     if (rc) return rc;
-    if (xnext) {
-        rc = check_block("beamform, next block", nch, ns_next, pitch_next);
-        if (rc) return rc;
-    } else if (ns_next != 0) {
-        return fail(D4W_EINVAL, "beamform: %d samples of a next block that is not given", ns_next);
-    }
     const size_t words = beam_part_words(nch, ncalls, length);
     if (words && !ws) return fail(D4W_EINVAL, "beamform: %d channels are more than one segment of %d and need the workspace", nch, kBeamSegment);
     float* part = (float*)ws;

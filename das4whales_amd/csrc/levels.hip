@@ -54,7 +54,6 @@ constexpr int kLevelGroup = kLevelThreads / kLevelChannels;  // lanes per channe
 constexpr int kLevelSlots = 64 / kLevelGroup;                // chains per lane
 constexpr int kLevelMaxCalls = 65535;                        // grid limit
 constexpr int kLevelMaxLength = 1 << 30;                     // of L and of N + gap
-constexpr long long kLevelStartMax = 1ll << 62;              // start is clamped here: the sums below cannot overflow
 
 // LevelWindow, level_window: taps.h (project.hip describes its windows the same way)
 
@@ -87,7 +86,7 @@ __global__ __launch_bounds__(kLevelThreads) void level_sum(const float* __restri
     const int c = blockIdx.y;
     const long long chl = (long long)blockIdx.x * kLevelChannels + kk;
     const long long ntot = (long long)ns + (long long)nsn;
-    const long long s0 = min(max(start[c], -kLevelStartMax), kLevelStartMax);
+    const long long s0 = clamp_start(start[c]);
     const float qnan = __int_as_float(0x7fc00000);
 
     const bool there = chl < nch;
@@ -173,15 +172,9 @@ int d4w_level_f32(const float* x, int64_t pitch, int nch, int ns, const float* x
     if (length < 1 || length > kLevelMaxLength) return fail(D4W_EINVAL, "level: the length %d is outside 1 .. %d", length, kLevelMaxLength);
     if (noise_length < 0 || gap < 0 || (long long)noise_length + (long long)gap > (long long)kLevelMaxLength)
         return fail(D4W_EINVAL, "level: noise_length %d and gap %d must be >= 0 and add up to at most %d", noise_length, gap, kLevelMaxLength);
-    int rc = check_block("level", nch, ns, pitch);
+    const int rc = check_record("level", nch, ns, pitch, xnext, ns_next, pitch_next);
     if (rc) return rc;
     if (nch > (1 << 30)) return fail(D4W_EINVAL, "level: %d channels, a launch takes 1 .. %d", nch, 1 << 30);
-    if (xnext) {
-        rc = check_block("level, next block", nch, ns_next, pitch_next);
-        if (rc) return rc;
-    } else if (ns_next != 0) {
-        return fail(D4W_EINVAL, "level: %d samples of a next block that is not given", ns_next);
-    }
     if (ncalls == 0) return D4W_OK;
     if (!x || !r || !start || !signal || !peak) return fail(D4W_EINVAL, "bad argument");
     if (noise_length > 0 && !noise) return fail(D4W_EINVAL, "level: a noise window of %d samples without a noise output", noise_length);

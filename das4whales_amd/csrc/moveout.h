@@ -53,12 +53,21 @@ __device__ __forceinline__ void moveout_split(double tau, int& k, float& f) {
     }
 }
 
-// host side: the checks of c0, fs, dt and of a [nch x ns] block with its row pitch that every entry point makes
+// host side: the checks of c0, fs, dt, of a [nch x ns] block with its row pitch and of a record that every entry point makes
 static inline bool positive_finite(double v) { return std::isfinite(v) && v > 0.0; }
 
 static inline int check_block(const char* who, int nch, int ns, long long pitch) {
     if (nch < 1 || ns < 1) return fail(D4W_EINVAL, "%s: the block %d x %d is empty", who, nch, ns);
     if (pitch < ns) return fail(D4W_EINVAL, "%s: the row pitch %lld is below the %d samples of a row", who, pitch, ns);
+    return D4W_OK;
+}
+
+// a record: the block and, behind it, the optional next block of the same channels (beam, align, levels, project)
+static inline int check_record(const char* who, int nch, int ns, long long pitch, const void* xnext, int ns_next, long long pitch_next) {
+    const int rc = check_block(who, nch, ns, pitch);
+    if (rc) return rc;
+    if (xnext) return check_block((std::string(who) + ", next block").c_str(), nch, ns_next, pitch_next);
+    if (ns_next != 0) return fail(D4W_EINVAL, "%s: %d samples of a next block that is not given", who, ns_next);
     return D4W_OK;
 }
 

@@ -65,7 +65,6 @@ constexpr int kProjGroup = kProjThreads / kProjChannels;     // lanes per channe
 constexpr int kProjSlots = 64 / kProjGroup;                  // chains per lane
 constexpr int kProjMaxCalls = 65535;                         // grid limit
 constexpr int kProjMaxLength = 1 << 30;                      // of the beam
-constexpr long long kProjStartMax = 1ll << 62;               // start is clamped here: the sums below cannot overflow
 constexpr int kProjChunk = 1024;                             // terms of a support per LDS piece of the beam: a multiple of 64
 constexpr int kSubThreads = 256;
 constexpr int kSubCpt = 8;                                   // samples per thread
@@ -85,7 +84,7 @@ template <int ORDER>
 __device__ __forceinline__ bool project_support(const long long* __restrict__ start, int c, const int* __restrict__ kr, size_t e, int W,
                                                 long long ntot, long long& lo) {
     constexpr int kLo = ORDER == 3 ? -1 : 0;
-    lo = min(max(start[c], -kProjStartMax), kProjStartMax) + (long long)kr[e] + kLo;
+    lo = clamp_start(start[c]) + (long long)kr[e] + kLo;
     return lo >= 0 && lo + W <= ntot;
 }
 
@@ -272,15 +271,9 @@ static int project_check(const char* who, int nch, int ns, long long pitch, cons
     if (ncalls < 0 || ncalls > kProjMaxCalls) return fail(D4W_EINVAL, "%s: %d calls, a launch takes 0 .. %d", who, ncalls, kProjMaxCalls);
     if (length < 1 || length > kProjMaxLength) return fail(D4W_EINVAL, "%s: the length %d is outside 1 .. %d", who, length, kProjMaxLength);
     if (order != 0 && order != 1 && order != 3) return fail(D4W_EINVAL, "%s: order %d is none of 0, 1, 3", who, order);
-    int rc = check_block(who, nch, ns, pitch);
+    const int rc = check_record(who, nch, ns, pitch, xnext, ns_next, pitch_next);
     if (rc) return rc;
     if (nch > (1 << 30)) return fail(D4W_EINVAL, "%s: %d channels, a launch takes 1 .. %d", who, nch, 1 << 30);
-    if (xnext) {
-        rc = check_block(who, nch, ns_next, pitch_next);
-        if (rc) return rc;
-    } else if (ns_next != 0) {
-        return fail(D4W_EINVAL, "%s: %d samples of a next block that is not given", who, ns_next);
-    }
     return D4W_OK;
 }
 

@@ -1,6 +1,7 @@
-// What the beam and its transpose share beyond the travel time (beam.hip, project.hip; levels.hip for the window): the
-// interpolation coefficients of a fractional delay and the description of a window of a row of the record.  One text each, so
-// that "the exact transpose of the beam's taps" and "the same window rule" are properties of this header.
+// What the beam and its transpose share beyond the travel time (beam.hip, project.hip; levels.hip for the window; align.hip
+// for the clamp): the interpolation coefficients of a fractional delay, the description of a window of a row of the record
+// and the clamp of a call's first sample.  One text each, so that "the exact transpose of the beam's taps", "the same window
+// rule" and "the same clamp" are properties of this header.
 #pragma once
 #include "moveout.h"
 
@@ -50,5 +51,11 @@ __device__ __forceinline__ LevelWindow level_window(const float* row, const floa
     }
     return w;
 }
+
+// the first emission sample of a call, clamped so that the sums of it, a delay and a length cannot overflow (beam.hip,
+// align.hip, levels.hip, project.hip)
+constexpr long long kStartMax = 1ll << 62;
+
+__device__ __forceinline__ long long clamp_start(long long start) { return min(max(start, -kStartMax), kStartMax); }
 
 }  // namespace d4w

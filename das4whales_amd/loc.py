@@ -22,6 +22,7 @@ Arrival times that are NaN mean "no pick on this channel": the solver and the gr
 notion -- its np.min(Ti) turns the whole result into NaN).
 """
 import ctypes
+import math
 import sys
 from types import SimpleNamespace
 
@@ -52,9 +53,14 @@ def _f64(x, device=None):
     return torch.from_numpy(a).to(device or ("cuda:%d" % torch.cuda.current_device()))
 
 
-# Two rules for the container of a result, different on purpose.  _back serves the functions that mirror the reference: a host
-# tensor in gives a host tensor back.  _out serves the later families (vote, stack, beam): any tensor in, on the host or on a
-# device, gives a tensor on the device the work ran on, and only NumPy in gives NumPy back.
+# Two rules for the container of a result, different on purpose.  _back serves the functions that mirror the reference and
+# their batched forms: a host tensor in gives a host tensor back.  It is the rule of calc_arrival_times, solve_lq,
+# calc_covariance_matrix, calc_uncertainty_position, solve_lq_batch, misfit_grid, first_guess_grid and solve_robust_batch
+# (relocate returns what its last solve_robust_batch does).  _out serves the later families: any tensor in, on the host or on a
+# device, gives a tensor on the device the work ran on, and only NumPy in gives NumPy back.  It is the rule of vote_grid,
+# associate_picks, delay_table, stack_grid, stack_best, arrivals_near, locate_stack, beam_delays, beamform, refine_arrivals,
+# received_levels, project_calls, subtract_calls and remove_calls.  The small arithmetic (the four per-channel helpers,
+# levels_db, fit_spreading) stays in the container it was given.
 def _back(y, *templates):
     """The device result in the callers' container: a tensor where any input was one (on the host if none was on a device)."""
     ts = [t for t in templates if dev.is_tensor(t)]
@@ -88,7 +94,7 @@ def _dtype_name(a):
 
 def _pos_finite(**kw):
     for name, v in kw.items():
-        if not (np.isfinite(v) and v > 0):
+        if not (math.isfinite(v) and v > 0):
             raise ValueError("%s must be positive and finite, got %r" % (name, v))
 
 
@@ -126,21 +132,54 @@ def _positions(pos, t0, device):
     return p, (None if t0 is _SKIP else _f64(t0, device).reshape(-1).expand(p.shape[0]).contiguous())
 
 
+def _p(t, write=False):
+    """The device pointer of t for the C call, NULL for None.  write=True: through dev.out_ptr, which bumps t's version."""
+    return None if t is None else (dev.out_ptr(t) if write else dev.ptr(t))
+
+
+def _whole(v, name, lo, hi=None):
+    """v as an int within lo .. hi, checked on the host."""
+    try:
+        ok = (type(v) is int or (not isinstance(v, bool) and _shape(v) == () and int(v) == v)) and v >= lo and (hi is None or v <= hi)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("%s must be a whole number of at least %d%s, got %r" % (name, lo, "" if hi is None else " and at most %d" % hi, v))
+    return int(v)
+
+
+def _number(v, name):
+    """v as a finite float, checked on the host."""
+    if isinstance(v, bool) or _shape(v) != () or not np.isfinite(v):
+        raise ValueError("%s must be a finite number, got %r" % (name, v))
+    return float(v)
+
+
+def _inplace_view(t, device=None):
+    """Whether t is a float32 CUDA tensor [rows x columns] with unit column stride (on `device`, when given): a block that is
+    read, and written, where it lies."""
+    return (dev.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
+            and (t.stride(0) >= t.shape[1] or t.shape[0] == 1) and (device is None or t.device == torch.device(device)))
+
+
 def _env_block(env, device):
     """(float32 CUDA tensor [nch x ns] with unit column stride, row pitch in elements).  A column-sliced float32 CUDA view is
     taken as it is; everything else becomes a contiguous float32 copy on the device."""
-    if (dev.is_tensor(env) and env.is_cuda and env.dtype == torch.float32 and env.device == torch.device(device)
-            and env.stride(1) == 1 and (env.stride(0) >= env.shape[1] or env.shape[0] == 1)):
+    if _inplace_view(env, device):
         return env, (env.stride(0) if env.shape[0] > 1 else env.shape[1])
     e = dev.to_device_f32(env, device)
     return e, e.shape[1]
 
 
-def _check(cable_pos, c0, fs, *, block=_SKIP, name="env", next_block=None, weights=None, xs=_SKIP, ys=_SKIP, pos=_SKIP, t0=_SKIP):
-    """The arguments the vote, the stack and the beam share, checked against each other on the host: a bad call raises
-    ValueError before any device work, with or without a GPU.  Returns the object _upload completes, so far with c0, fs and the
-    sizes nch, ns (block), nx, ny (grid axes) and ncalls (positions); a function's own checks go between the two."""
-    a = SimpleNamespace(c0=float(c0), fs=float(fs), nch=_channels(cable_pos))
+def _check(cable_pos, c0, fs, *, block=_SKIP, name="env", next_block=None, weights=None, xs=_SKIP, ys=_SKIP, pos=_SKIP, t0=_SKIP,
+           start=_SKIP, table=_SKIP, limits=None):
+    """The arguments the localisation families share, checked against each other on the host: a bad call raises ValueError
+    before any device work, with or without a GPU.  Beyond the geometry, for the calls that read a record along a moveout:
+    start (an int or [ncalls] ints), table = (delays, kind) with kind "r" (beam_delays(rounded=True), int32) or "kf" (the pair
+    (k int32, f float32)) and delays None for tables built from the positions, and limits = (most calls, largest length) of one
+    launch.  Returns the object _upload completes, so far with c0, fs, the sizes nch, ns and ns_nb (block, next block), nx, ny
+    (grid axes), ncalls (positions), max_calls and max_length (limits) and kind; a function's own checks go between the two."""
+    a = SimpleNamespace(c0=float(c0), fs=float(fs), nch=_channels(cable_pos), ns_nb=0, kind=None, tables=())
     _pos_finite(c0=a.c0, fs=a.fs)
     for what, b in ((name, block), ("next_block", next_block)):
         if b is _SKIP or b is None:
@@ -151,6 +190,8 @@ def _check(cable_pos, c0, fs, *, block=_SKIP, name="env", next_block=None, weigh
             raise ValueError("%s has %d rows, cable_pos %d channels" % (what, b.shape[0], a.nch))
     if block is not _SKIP:
         a.ns = block.shape[1]
+    if next_block is not None:
+        a.ns_nb = next_block.shape[1]
     if weights is not None and _count(weights) != a.nch:
         raise ValueError("weights must hold one value per channel (%d), got shape %s" % (a.nch, _shape(weights)))
     if xs is not _SKIP:
@@ -159,18 +200,39 @@ def _check(cable_pos, c0, fs, *, block=_SKIP, name="env", next_block=None, weigh
             raise ValueError("the grid needs at least one node")
     if pos is not _SKIP:
         a.ncalls = _npos(pos, t0)
-    a.given = (block, cable_pos, xs, ys, pos, t0, weights, next_block)
+    if limits is not None:
+        a.max_calls, a.max_length = limits
+        if a.ncalls > a.max_calls:
+            raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, a.max_calls))
+    if start is not _SKIP:
+        ss = _shape(start)
+        if ss not in ((), (a.ncalls,)) or _dtype_name(start)[:3] not in ("int", "uin"):
+            raise ValueError("start must be an int or [ncalls] = (%d,) ints, got shape %s of %s" % (a.ncalls, ss, _dtype_name(start)))
+    if table is not _SKIP:
+        delays, a.kind = table
+        if delays is not None:
+            want = (("r", "int32"),) if a.kind == "r" else (("k", "int32"), ("f", "float32"))
+            a.tables = (delays,) if a.kind == "r" else tuple(delays)
+            if len(a.tables) != len(want):
+                raise ValueError("delays must be the pair (k, f) of beam_delays()")
+            for t, (what, dtype) in zip(a.tables, want):
+                if _shape(t) != (a.ncalls, a.nch) or _dtype_name(t) != dtype:
+                    raise ValueError("delays: %s must be %s [ncalls x channel] = %s, got %s %s"
+                                     % (what, dtype, (a.ncalls, a.nch), _dtype_name(t), _shape(t)))
+    a.given = (block, cable_pos, xs, ys, pos, t0, weights, next_block, start)
     return a
 
 
 def _upload(a, like=(), device=None):
     """The arguments of _check on one device: cable [nch x 3], e and pitch (the block; nb and pitch_nb the next one), w [nch] or
-    None, gx and gy, p [ncalls x 3] and t [ncalls] or None, each where it was given.  The device is `device`, or that of the
-    first CUDA tensor among the arguments and `like`, or the current one; as_tensor says whether any of them is a tensor."""
-    block, cable_pos, xs, ys, pos, t0, weights, next_block = given = a.given
+    None, gx and gy, p [ncalls x 3] and t [ncalls] or None, s (start as int64 [ncalls]) and the delay tables kr (k or r) and f
+    (or None), given or built from p, each where it was asked for.  The device is `device`, or that of the first CUDA tensor
+    among the arguments, `like` and the tables, or the current one; as_tensor says whether any of them is a tensor."""
+    block, cable_pos, xs, ys, pos, t0, weights, next_block, start = a.given
+    given = a.given + tuple(like) + a.tables
     del a.given
-    a.as_tensor = any(dev.is_tensor(x) for x in given + tuple(like))
-    a.cable = _f64(cable_pos, device if device is not None else _device_of(*(given + tuple(like))))
+    a.as_tensor = any(dev.is_tensor(x) for x in given)
+    a.cable = _f64(cable_pos, device if device is not None else _device_of(*given))
     d = a.device = a.cable.device
     if block is not _SKIP:
         a.e, a.pitch = _env_block(block, d)
@@ -182,7 +244,27 @@ def _upload(a, like=(), device=None):
         a.gx, a.gy = _f64(xs, d).reshape(-1), _f64(ys, d).reshape(-1)
     if pos is not _SKIP:
         a.p, a.t = _positions(pos, t0, d)
+    if start is not _SKIP:
+        s = start.to(d, torch.int64) if dev.is_tensor(start) else torch.from_numpy(np.array(start, dtype=np.int64)).to(d)
+        a.s = s.reshape(-1).expand(a.ncalls).contiguous()
+    if a.kind is not None:
+        a.kr, a.f = _tables(a)
     return a
+
+
+def _record(a):
+    """The record prefix of the C calls that read one: the block with its pitch and sizes, the next block (or NULL) with its."""
+    return dev.ptr(a.e), a.pitch, a.nch, a.ns, _p(a.nb), a.pitch_nb, a.ns_nb
+
+
+def _waveforms(x, name, a):
+    """The check of one float32 waveform per call (refine_arrivals' template, the beam of project_calls): their length."""
+    xs = _shape(x)
+    if not ((len(xs) == 2 and xs[0] == a.ncalls) or (len(xs) == 1 and a.ncalls == 1)) or _dtype_name(x) != "float32":
+        raise ValueError("%s must be float32 [ncalls x L] = (%d, L) (or [L] for one call), got %s %s" % (name, a.ncalls, _dtype_name(x), xs))
+    if xs[-1] < 1 or xs[-1] > a.max_length:
+        raise ValueError("the length %d of %s is outside 1 .. %d" % (xs[-1], name, a.max_length))
+    return xs[-1]
 
 
 def _calls(Ti, nch, device):
@@ -196,6 +278,18 @@ def _calls(Ti, nch, device):
     return t, single
 
 
+def _first_guess(first_guess, ncalls, device):
+    """first_guess ([4] for every call, or [ncalls x 4]) as [ncalls x 4] on the device; None stays None."""
+    if first_guess is None:
+        return None
+    fg = _f64(first_guess, device)
+    if fg.dim() == 1:
+        fg = fg.reshape(1, -1).expand(ncalls, -1).contiguous()
+    if tuple(fg.shape) != (ncalls, 4):
+        raise ValueError("first_guess must be [x, y, z, t0] per call (%d x 4), got %s" % (ncalls, tuple(fg.shape)))
+    return fg
+
+
 def _solve(t, cable, c0, Nbiter, fix_z, first_guess):
     """The kernel on [ncalls][nch]: history, n, G^T G, sum of squared residuals, pick count (device tensors)."""
     ncalls, nch = t.shape
@@ -204,13 +298,7 @@ def _solve(t, cable, c0, Nbiter, fix_z, first_guess):
     if Nbiter < 0:
         raise ValueError("Nbiter must not be negative")
     d = t.device
-    fg = None
-    if first_guess is not None:
-        fg = _f64(first_guess, d)
-        if fg.dim() == 1:
-            fg = fg.reshape(1, -1).expand(ncalls, -1).contiguous()
-        if tuple(fg.shape) != (ncalls, 4):
-            raise ValueError("first_guess must be [x, y, z, t0] per call (%d x 4), got %s" % (ncalls, tuple(fg.shape)))
+    fg = _first_guess(first_guess, ncalls, d)
     with torch.cuda.device(d):
         hist = torch.empty((ncalls, Nbiter, 4), dtype=torch.float64, device=d)
         n = torch.empty((ncalls, 4), dtype=torch.float64, device=d)
@@ -218,9 +306,8 @@ def _solve(t, cable, c0, Nbiter, fix_z, first_guess):
         ssr = torch.empty((ncalls,), dtype=torch.float64, device=d)
         npick = torch.empty((ncalls,), dtype=torch.int32, device=d)
         _lib.check(_lib.lib.d4w_loc_solve_f64(dev.ptr(cable), nch, dev.ptr(t), ncalls, float(c0), Nbiter, int(bool(fix_z)),
-                                              dev.ptr(fg) if fg is not None else None, dev.out_ptr(hist) if Nbiter else None,
-                                              dev.out_ptr(n), dev.out_ptr(gtg), dev.out_ptr(ssr), dev.out_ptr(npick),
-                                              dev.stream_ptr(t)))
+                                              _p(fg), dev.out_ptr(hist) if Nbiter else None, dev.out_ptr(n), dev.out_ptr(gtg),
+                                              dev.out_ptr(ssr), dev.out_ptr(npick), dev.stream_ptr(t)))
     return hist, n, gtg, ssr, npick
 
 
@@ -243,6 +330,18 @@ def _covariance(gtg, var, quiet=False):
             a = a + LAMBDA_REG * np.eye(p)
         cov[k] = var[k] * np.linalg.inv(a)
     return cov
+
+
+def _stats(gtg, ssr, count, p, count_name, given):
+    """The statistics the two batched solvers share, from the kernel's G^T G, sum of squared residuals and channel count per
+    call: variance, covariance, uncertainty and the count under the solver's own name, in the callers' container (_back)."""
+    cnt = count.cpu().numpy().astype(np.int64)
+    with np.errstate(all="ignore"):
+        var = np.where(cnt > p, ssr.cpu().numpy() / np.maximum(cnt - p, 1), np.nan)
+        cov = _covariance(np.where((cnt > 0)[:, None, None], gtg.cpu().numpy(), np.nan), var, quiet=True)
+        unc = np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
+    stats = {"variance": var, "covariance": cov, "uncertainty": unc, count_name: cnt}
+    return {k: _back(torch.from_numpy(np.ascontiguousarray(v)).to(gtg.device), *given) for k, v in stats.items()}
 
 
 # ------------------------------------------------------------------------------------------
@@ -371,22 +470,14 @@ def solve_lq_batch(Ti, cable_pos, c0, Nbiter=10, fix_z=False, first_guess=None, 
     hist, n, gtg, ssr, npick = _solve(t, cable, c0, Nbiter, fix_z, first_guess)
     if not return_stats:
         return _back(n, Ti, cable_pos)
-    p = 3 if fix_z else 4
-    cnt = npick.cpu().numpy().astype(np.int64)
-    with np.errstate(all="ignore"):
-        var = np.where(cnt > p, ssr.cpu().numpy() / np.maximum(cnt - p, 1), np.nan)
-        cov = _covariance(np.where((cnt > 0)[:, None, None], gtg.cpu().numpy(), np.nan), var, quiet=True)
-        unc = np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
-    stats = {"variance": var, "covariance": cov, "uncertainty": unc, "npicks": cnt}
-    stats = {k: _back(torch.from_numpy(np.ascontiguousarray(v)).to(t.device), Ti, cable_pos) for k, v in stats.items()}
+    stats = _stats(gtg, ssr, npick, 3 if fix_z else 4, "npicks", (Ti, cable_pos))
     stats["history"] = _back(hist, Ti, cable_pos)
     return _back(n, Ti, cable_pos), stats
 
 
-def misfit_grid(Ti, cable_pos, c0, xs, ys, z):
-    """For every call and every node (xs[ix], ys[iy], z): the best emission time t0 = mean over the picked channels of
-    Ti - distance / c0, and the RMS residual once it is removed.  Returns (rms, t0), each [ncalls x ny x nx] ([ny x nx] for
-    one call given as a vector).  The minimum of rms is the first guess solve_lq needs (first_guess_grid)."""
+def _misfit(Ti, cable_pos, c0, xs, ys, z):
+    """misfit_grid on the device, shared with first_guess_grid: (gx, gy, whether one call came as a vector, rms, t0 as
+    [ncalls x ny x nx])."""
     cable = _cable(cable_pos, _device_of(Ti, cable_pos))
     t, single = _calls(Ti, cable.shape[0], cable.device)
     gx, gy = _f64(xs, cable.device).reshape(-1), _f64(ys, cable.device).reshape(-1)
@@ -399,6 +490,14 @@ def misfit_grid(Ti, cable_pos, c0, xs, ys, z):
             _lib.check(_lib.lib.d4w_loc_misfit_grid_f64(dev.ptr(cable), nch, dev.ptr(t[a:b]), b - a, float(c0), dev.ptr(gx), gx.numel(),
                                                         dev.ptr(gy), gy.numel(), float(z), dev.out_ptr(rms[a:b]),
                                                         dev.out_ptr(t0[a:b]), dev.stream_ptr(cable)))
+    return gx, gy, single, rms, t0
+
+
+def misfit_grid(Ti, cable_pos, c0, xs, ys, z):
+    """For every call and every node (xs[ix], ys[iy], z): the best emission time t0 = mean over the picked channels of
+    Ti - distance / c0, and the RMS residual once it is removed.  Returns (rms, t0), each [ncalls x ny x nx] ([ny x nx] for
+    one call given as a vector).  The minimum of rms is the first guess solve_lq needs (first_guess_grid)."""
+    _, _, single, rms, t0 = _misfit(Ti, cable_pos, c0, xs, ys, z)
     if single:
         rms, t0 = rms[0], t0[0]
     return _back(rms, Ti, cable_pos), _back(t0, Ti, cable_pos)
@@ -407,11 +506,8 @@ def misfit_grid(Ti, cable_pos, c0, xs, ys, z):
 def first_guess_grid(Ti, cable_pos, c0, xs, ys, z):
     """The node of smallest RMS misfit per call as [x, y, z, t0] ([ncalls x 4], or [4] for one call given as a vector), ready to
     pass as `first_guess`.  A call without a pick gives a NaN row."""
-    cable = _cable(cable_pos, _device_of(Ti, cable_pos))
-    t, single = _calls(Ti, cable.shape[0], cable.device)
-    gx, gy = _f64(xs, cable.device).reshape(-1), _f64(ys, cable.device).reshape(-1)
-    rms, t0 = misfit_grid(t, cable, c0, gx, gy, z)
-    ncalls = t.shape[0]
+    gx, gy, single, rms, t0 = _misfit(Ti, cable_pos, c0, xs, ys, z)
+    ncalls = rms.shape[0]
     flat = torch.nan_to_num(rms.reshape(ncalls, -1), nan=float("inf"))
     k = torch.argmin(flat, dim=1)
     out = torch.stack([gx[k % gx.numel()], gy[k // gx.numel()], torch.full_like(gx[k % gx.numel()], float(z)),
@@ -508,10 +604,9 @@ def _assoc_setup(picks, fs, cable_pos, c0, xs, ys, z, dt, t0_range):
 
 def _vote(packed, idx, sign, accumulate, cable, fs, c0, gx, gy, z, lo, dt, nbins, votes, stop):
     K = packed.shape[1]
-    _lib.check(_lib.lib.d4w_assoc_vote_i32(dev.ptr(packed) if K else None, K, dev.ptr(idx) if idx is not None else None,
-                                           idx.numel() if idx is not None else 0, sign, accumulate, dev.ptr(cable), cable.shape[0],
-                                           fs, c0, dev.ptr(gx), gx.numel(), dev.ptr(gy), gy.numel(), z, lo, dt, nbins,
-                                           dev.out_ptr(votes), dev.ptr(stop) if stop is not None else None, dev.stream_ptr(cable)))
+    _lib.check(_lib.lib.d4w_assoc_vote_i32(dev.ptr(packed) if K else None, K, _p(idx), idx.numel() if idx is not None else 0, sign,
+                                           accumulate, dev.ptr(cable), cable.shape[0], fs, c0, dev.ptr(gx), gx.numel(), dev.ptr(gy),
+                                           gy.numel(), z, lo, dt, nbins, dev.out_ptr(votes), _p(stop), dev.stream_ptr(cable)))
 
 
 def vote_grid(picks, fs, cable_pos, c0, xs, ys, z, dt, t0_range=None):
@@ -622,8 +717,8 @@ def _stack(e, pitch, table, w, nx, ny, k0, k1, normalize, form=0):
     nch, ns = e.shape
     out = torch.empty((ny, nx, k1 - k0), dtype=torch.float32, device=e.device)
     info = torch.empty(2, dtype=torch.int32, device=e.device)
-    _lib.check(_lib.lib.d4w_stack_grid_f32(dev.ptr(e), pitch, nch, ns, dev.ptr(table), dev.ptr(w) if w is not None else None, nx, ny,
-                                           k0, k1, int(bool(normalize)), form, dev.out_ptr(out), dev.out_ptr(info), dev.stream_ptr(e)))
+    _lib.check(_lib.lib.d4w_stack_grid_f32(dev.ptr(e), pitch, nch, ns, dev.ptr(table), _p(w), nx, ny, k0, k1, int(bool(normalize)), form,
+                                           dev.out_ptr(out), dev.out_ptr(info), dev.stream_ptr(e)))
     return out, info
 
 
@@ -702,8 +797,8 @@ def _arrivals(a, p, t, h, threshold):
     if ncalls:
         thr = _f64(threshold, a.device).reshape(-1) if _per_channel(threshold, a.nch) else None
         _lib.check(_lib.lib.d4w_stack_arrivals_f64(dev.ptr(a.e), a.pitch, a.nch, a.ns, a.fs, dev.ptr(a.cable), a.c0, dev.ptr(p), dev.ptr(t), ncalls,
-                                                   h, 0.0 if thr is not None else float(threshold), dev.ptr(thr) if thr is not None else None,
-                                                   dev.ptr(a.w) if a.w is not None else None, dev.out_ptr(Ti), dev.stream_ptr(a.cable)))
+                                                   h, 0.0 if thr is not None else float(threshold), _p(thr), _p(a.w), dev.out_ptr(Ti),
+                                                   dev.stream_ptr(a.cable)))
     return Ti
 
 
@@ -714,9 +809,7 @@ def arrivals_near(env, fs, cable_pos, c0, pos, t0, halfwidth, threshold, weights
     Returns Ti [ncalls x channel] float64 = sample / fs, NaN where the window misses the record, weights[ch] = 0, or the
     maximum is below `threshold` (a scalar or one value per channel): the form associate_picks returns and solve_lq_batch
     takes.  pos: [ncalls x 3] (or [3] with a scalar t0: one call, Ti still [1 x channel])."""
-    h = int(halfwidth)
-    if h < 0 or h != halfwidth:
-        raise ValueError("halfwidth must be a non-negative number of samples")
+    h = _whole(halfwidth, "halfwidth", 0)
     a = _check(cable_pos, c0, fs, block=env, weights=weights, pos=pos, t0=t0)
     if a.ncalls:
         _per_channel(threshold, a.nch)
@@ -743,11 +836,7 @@ def locate_stack(env, fs, cable_pos, c0, xs, ys, z, threshold, halfwidth, pick_t
     small torch operations on the [ncalls x channel] result.  See stack_grid for env (bring it to the rate wanted with dsp.decimate /
     dsp.resample_poly first), weights, k_range and normalize, arrivals_near for halfwidth and pick_threshold."""
     from . import detect
-    max_calls = int(max_calls)
-    if max_calls < 0:
-        raise ValueError("max_calls must not be negative")
-    if int(halfwidth) < 0:
-        raise ValueError("halfwidth must be a non-negative number of samples")
+    max_calls, h = _whole(max_calls, "max_calls", 0), _whole(halfwidth, "halfwidth", 0)
     a, stack, times = _stack_grid(env, fs, cable_pos, c0, xs, ys, z, weights, k_range, normalize)
     d, nx = a.device, a.nx
     with torch.cuda.device(d):
@@ -763,7 +852,7 @@ def locate_stack(env, fs, cable_pos, c0, xs, ys, z, threshold, halfwidth, pick_t
         fg[:, 0], fg[:, 1] = a.gx.cpu().numpy()[nodes % nx], a.gy.cpu().numpy()[nodes // nx]
         fg[:, 2], fg[:, 3] = a.z, times[cols]
         fg_d = torch.from_numpy(fg).to(d)
-        Ti = _arrivals(a, fg_d[:, :3].contiguous(), fg_d[:, 3].contiguous(), int(halfwidth), pick_threshold)
+        Ti = _arrivals(a, fg_d[:, :3].contiguous(), fg_d[:, 3].contiguous(), h, pick_threshold)
         info = {"first_guess": fg_d, "node": torch.from_numpy(nodes.astype(np.int32)).to(d),
                 "column": torch.from_numpy(cols.astype(np.int32)).to(d), "value": torch.from_numpy(peak_h[cols]).to(d),
                 "npicks": (~torch.isnan(Ti)).sum(1).to(torch.int32), "times": torch.from_numpy(times).to(d)}
@@ -783,14 +872,6 @@ def beam_limits():
     return a.value, b.value, s.value, t.value
 
 
-def _beam_args(cable_pos, c0, fs, pos, **kw):
-    """_check for beam_delays and beamform: the batch of positions must fit one launch as well."""
-    a = _check(cable_pos, c0, fs, pos=pos, **kw)
-    if a.ncalls > beam_limits()[0]:
-        raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, beam_limits()[0]))
-    return a
-
-
 def _beam_delays(a, rounded):
     """r (rounded) or (k, f), each [ncalls x nch], for the positions a.p."""
     shape = (a.ncalls, a.nch)
@@ -798,8 +879,7 @@ def _beam_delays(a, rounded):
     k = None if rounded else torch.empty(shape, dtype=torch.int32, device=a.device)
     f = None if rounded else torch.empty(shape, dtype=torch.float32, device=a.device)
     if a.ncalls:
-        _lib.check(_lib.lib.d4w_beam_delays(dev.ptr(a.cable), a.nch, a.c0, a.fs, dev.ptr(a.p), a.ncalls, dev.out_ptr(k) if k is not None else None,
-                                            dev.out_ptr(f) if f is not None else None, dev.out_ptr(r) if r is not None else None,
+        _lib.check(_lib.lib.d4w_beam_delays(dev.ptr(a.cable), a.nch, a.c0, a.fs, dev.ptr(a.p), a.ncalls, _p(k, True), _p(f, True), _p(r, True),
                                             dev.stream_ptr(a.cable)))
     return r if rounded else (k, f)
 
@@ -813,7 +893,7 @@ def beam_delays(cable_pos, c0, fs, pos, rounded=False):
     a NaN lands as well): what beamform(order=0, delays=...) takes.
     The tables depend on the geometry, the rate and the positions only.  NumPy in -> NumPy out; a CUDA tensor in -> tensors on that
     device and stream."""
-    a = _upload(_beam_args(cable_pos, c0, fs, pos))
+    a = _upload(_check(cable_pos, c0, fs, pos=pos, limits=beam_limits()[:2]))
     with torch.cuda.device(a.device):
         d = _beam_delays(a, bool(rounded))
     return _out(d, a.as_tensor) if rounded else (_out(d[0], a.as_tensor), _out(d[1], a.as_tensor))
@@ -824,43 +904,32 @@ def _given_table(t, device):
     return t.to(device).contiguous()
 
 
-def _beam_check(a, start, length, order, delays):
-    """The arguments only beamform has against the shared ones, on the host before any device work:
-    (length, the given delay tables as a tuple)."""
-    nt = a.ns if length is None else length
-    if isinstance(nt, bool) or nt != int(nt) or nt < 1:
-        raise ValueError("length must be a positive number of samples, got %r" % (length,))
-    nt = int(nt)
-    if nt > beam_limits()[1]:
-        raise ValueError("length %d is more than the %d one launch takes" % (nt, beam_limits()[1]))
-    ss = _shape(start)
-    if ss not in ((), (a.ncalls,)) or _dtype_name(start)[:3] not in ("int", "uin"):
-        raise ValueError("start must be an int or [ncalls] = (%d,) ints, got shape %s of %s" % (a.ncalls, ss, _dtype_name(start)))
-    tables = ()
-    if delays is not None:
-        tables = (delays,) if order == 0 else tuple(delays)
-        want = (("r", "int32"),) if order == 0 else (("k", "int32"), ("f", "float32"))
-        if len(tables) != len(want):
-            raise ValueError("delays must be (k, f) for order %d" % order)
-        for t, (name, dtype) in zip(tables, want):
-            if _shape(t) != (a.ncalls, a.nch) or _dtype_name(t) != dtype:
-                raise ValueError("delays: %s must be %s [ncalls x channel] = %s, got %s %s" % (name, dtype, (a.ncalls, a.nch), _dtype_name(t), _shape(t)))
-    return nt, tables
+def _tables(a):
+    """(k or r, f or None) on the device: the given tables, or beam_delays' for the positions a.p."""
+    if a.tables:
+        t = [_given_table(t, a.device) for t in a.tables]
+        return t[0], (t[1] if a.kind == "kf" else None)
+    with torch.cuda.device(a.device):                        # the one launch of _upload: given tables need no device context
+        return (_beam_delays(a, True), None) if a.kind == "r" else _beam_delays(a, False)
 
 
-def _beam(a, kr, f, start, nt, order, normalize):
+def _order(order):
+    """(order as an int, the kind of delay table it reads along)."""
+    if isinstance(order, bool) or order not in (0, 1, 3):
+        raise ValueError("order must be 0, 1 or 3, got %r" % (order,))
+    return int(order), ("r" if order == 0 else "kf")
+
+
+def _beam(a, nt, order, normalize):
     """The kernel on device tensors: beam [ncalls x nt] float32; no launch without a call."""
     out = torch.empty((a.ncalls, nt), dtype=torch.float32, device=a.device)
     if not a.ncalls:
         return out
-    nb, w = a.nb, a.w
     nbytes = ctypes.c_size_t()
     _lib.check(_lib.lib.d4w_beam_ws_bytes(a.nch, a.ncalls, nt, ctypes.byref(nbytes)))
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=a.device) if nbytes.value else None
-    _lib.check(_lib.lib.d4w_beamform_f32(dev.ptr(a.e), a.pitch, a.nch, a.ns, dev.ptr(nb) if nb is not None else None, a.pitch_nb,
-                                         nb.shape[1] if nb is not None else 0, dev.ptr(kr), dev.ptr(f) if f is not None else None,
-                                         dev.ptr(w) if w is not None else None, dev.ptr(start), a.ncalls, nt, order, int(bool(normalize)),
-                                         dev.out_ptr(out), dev.out_ptr(ws) if ws is not None else None, dev.stream_ptr(a.e)))
+    _lib.check(_lib.lib.d4w_beamform_f32(*_record(a), dev.ptr(a.kr), _p(a.f), _p(a.w), dev.ptr(a.s), a.ncalls, nt, order, int(bool(normalize)),
+                                         dev.out_ptr(out), _p(ws, True), dev.stream_ptr(a.e)))
     return out
 
 
@@ -887,27 +956,15 @@ def beamform(trace, fs, cable_pos, c0, pos, start=0, length=None, order=1, weigh
     float32 sums in increasing channel order in fixed segments of beam_limits()[2] channels, the segment partials added in
     increasing order: run-to-run bit-identical, independent of the other calls of the batch and of a power-of-two scaling of trace.
     NumPy in -> NumPy out; a CUDA tensor in -> tensors on that device and stream."""
-    if isinstance(order, bool) or order not in (0, 1, 3):
-        raise ValueError("order must be 0, 1 or 3, got %r" % (order,))
-    order = int(order)
-    a = _beam_args(cable_pos, c0, fs, pos, block=trace, name="trace", next_block=next_block, weights=weights)
-    nt, tables = _beam_check(a, start, length, order, delays)
-    _upload(a, like=(start,) + tables)
-    d = a.device
-    if dev.is_tensor(start):
-        s = start.to(d, torch.int64).reshape(-1)
-    else:
-        s = torch.from_numpy(np.array(start, dtype=np.int64).reshape(-1)).to(d)
-    s = s.expand(a.ncalls).contiguous()
+    order, kind = _order(order)
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights, start=start,
+               table=(delays, kind), limits=beam_limits()[:2])
+    nt = _whole(a.ns if length is None else length, "length", 1, a.max_length)
+    d = _upload(a).device
     with torch.cuda.device(d):
-        if delays is None:
-            kr, f = (_beam_delays(a, True), None) if order == 0 else _beam_delays(a, False)
-        else:
-            kr = _given_table(tables[0], d)
-            f = _given_table(tables[1], d) if order else None
-        out = _beam(a, kr, f, s, nt, order, normalize)
+        out = _beam(a, nt, order, normalize)
         # a tensor divisor: a true division (by a Python number torch multiplies with the reciprocal instead)
-        times = (s.to(torch.float64)[:, None] + torch.arange(nt, dtype=torch.float64, device=d)[None, :]) \
+        times = (a.s.to(torch.float64)[:, None] + torch.arange(nt, dtype=torch.float64, device=d)[None, :]) \
             / torch.full((), a.fs, dtype=torch.float64, device=d)
     return _out(out, a.as_tensor), _out(times, a.as_tensor)
 
@@ -920,36 +977,6 @@ def align_limits():
     a, b, m, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     _lib.check(_lib.lib.d4w_align_limits(ctypes.byref(a), ctypes.byref(b), ctypes.byref(m), ctypes.byref(w)))
     return a.value, b.value, m.value, w.value
-
-
-def _align_check(a, template, start, max_lag, min_coef, delays):
-    """The arguments only refine_arrivals has against the shared ones, on the host before any device work: (L, M, min_coef)."""
-    max_calls, max_length, max_m, _ = align_limits()
-    if a.ncalls > max_calls:
-        raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, max_calls))
-    ts = _shape(template)
-    if not ((len(ts) == 2 and ts[0] == a.ncalls) or (len(ts) == 1 and a.ncalls == 1)) or _dtype_name(template) != "float32":
-        raise ValueError("template must be float32 [ncalls x L] = (%d, L) (or [L] for one call), got %s %s" % (a.ncalls, _dtype_name(template), ts))
-    L = ts[-1]
-    if L < 1 or L > max_length:
-        raise ValueError("the template length %d is outside 1 .. %d" % (L, max_length))
-    ss = _shape(start)
-    if ss not in ((), (a.ncalls,)) or _dtype_name(start)[:3] not in ("int", "uin"):
-        raise ValueError("start must be an int or [ncalls] = (%d,) ints, got shape %s of %s" % (a.ncalls, ss, _dtype_name(start)))
-    try:
-        whole = not isinstance(max_lag, bool) and _shape(max_lag) == () and int(max_lag) == max_lag and max_lag >= 0
-    except (TypeError, ValueError, OverflowError):
-        whole = False
-    if not whole:
-        raise ValueError("max_lag must be a non-negative number of samples, got %r" % (max_lag,))
-    if max_lag > max_m:
-        raise ValueError("max_lag %d is more than the %d one launch takes" % (max_lag, max_m))
-    if isinstance(min_coef, bool) or _shape(min_coef) != () or not np.isfinite(min_coef):
-        raise ValueError("min_coef must be a finite number, got %r" % (min_coef,))
-    if delays is not None and (_shape(delays) != (a.ncalls, a.nch) or _dtype_name(delays) != "int32"):
-        raise ValueError("delays must be int32 [ncalls x channel] = %s (beam_delays(rounded=True)), got %s %s"
-                         % ((a.ncalls, a.nch), _dtype_name(delays), _shape(delays)))
-    return L, int(max_lag), float(min_coef)
 
 
 def refine_arrivals(trace, fs, cable_pos, c0, pos, template, start, max_lag, min_coef=0.0, weights=None, next_block=None, subsample=True,
@@ -988,15 +1015,11 @@ def refine_arrivals(trace, fs, cable_pos, c0, pos, template, start, max_lag, min
     The sums are float32 in an order that depends on L alone: run-to-run bit-identical, independent of the other calls of the
     batch, and rho keeps its bits under a power-of-two scaling of trace or template.  NumPy in -> NumPy out; any tensor in ->
     tensors on that device and stream."""
-    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights)
-    L, M, min_coef = _align_check(a, template, start, max_lag, min_coef, delays)
-    _upload(a, like=(start, template, delays))
-    d = a.device
-    if dev.is_tensor(start):
-        s = start.to(d, torch.int64).reshape(-1)
-    else:
-        s = torch.from_numpy(np.array(start, dtype=np.int64).reshape(-1)).to(d)
-    s = s.expand(a.ncalls).contiguous()
+    limits = align_limits()
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights, start=start,
+               table=(delays, "r"), limits=limits[:2])
+    L, M, min_coef = _waveforms(template, "template", a), _whole(max_lag, "max_lag", 0, limits[2]), _number(min_coef, "min_coef")
+    d = _upload(a, like=(template,)).device
     with torch.cuda.device(d):
         Ti = torch.empty((a.ncalls, a.nch), dtype=torch.float64, device=d)
         coef = torch.empty((a.ncalls, a.nch), dtype=torch.float32, device=d)
@@ -1004,13 +1027,9 @@ def refine_arrivals(trace, fs, cable_pos, c0, pos, template, start, max_lag, min
         rho = torch.empty((a.ncalls, a.nch, 2 * M + 1), dtype=torch.float32, device=d) if return_all else None
         if a.ncalls:
             t = _given_table(template, d).reshape(a.ncalls, L)
-            r = _beam_delays(a, True) if delays is None else _given_table(delays, d)
-            nb, w = a.nb, a.w
-            _lib.check(_lib.lib.d4w_align_f32(dev.ptr(a.e), a.pitch, a.nch, a.ns, dev.ptr(nb) if nb is not None else None, a.pitch_nb,
-                                              nb.shape[1] if nb is not None else 0, dev.ptr(t), L, dev.ptr(r), dev.ptr(s), a.ncalls, M,
-                                              dev.ptr(w) if w is not None else None, a.fs, min_coef, int(bool(subsample)), dev.out_ptr(Ti),
-                                              dev.out_ptr(coef), dev.out_ptr(lag) if lag is not None else None,
-                                              dev.out_ptr(rho) if rho is not None else None, dev.stream_ptr(a.e)))
+            _lib.check(_lib.lib.d4w_align_f32(*_record(a), dev.ptr(t), L, dev.ptr(a.kr), dev.ptr(a.s), a.ncalls, M, _p(a.w), a.fs, min_coef,
+                                              int(bool(subsample)), dev.out_ptr(Ti), dev.out_ptr(coef), _p(lag, True), _p(rho, True),
+                                              dev.stream_ptr(a.e)))
     out = (Ti, coef) + ((lag, rho) if return_all else ())
     return tuple(_out(y, a.as_tensor) for y in out)
 
@@ -1028,17 +1047,6 @@ def robust_limits():
     a, b = ctypes.c_int(), ctypes.c_int()
     _lib.check(_lib.lib.d4w_loc_robust_limits(ctypes.byref(a), ctypes.byref(b)))
     return a.value, b.value
-
-
-def _whole(v, name, lo, hi=None):
-    """v as an int within lo .. hi, checked on the host."""
-    try:
-        ok = not isinstance(v, bool) and _shape(v) == () and int(v) == v and v >= lo and (hi is None or v <= hi)
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError("%s must be a whole number of at least %d%s, got %r" % (name, lo, "" if hi is None else " and at most %d" % hi, v))
-    return int(v)
 
 
 def _robust_check(Ti, cable_pos, c0, weights, loss, tuning, scale, Nbiter, warmup, first_guess):
@@ -1109,11 +1117,7 @@ def solve_robust_batch(Ti, cable_pos, c0, weights=None, loss="huber", tuning=Non
     d = cable.device
     t = _f64(Ti, d)
     w = _f64(weights, d) if weights is not None else None
-    fg = None
-    if first_guess is not None:
-        fg = _f64(first_guess, d)
-        if fg.dim() == 1:
-            fg = fg.reshape(1, -1).expand(ncalls, -1).contiguous()
+    fg = _first_guess(first_guess, ncalls, d)
     p = 3 if fix_z else 4
     lib = _lib.lib
     with torch.cuda.device(d):
@@ -1128,21 +1132,13 @@ def solve_robust_batch(Ti, cable_pos, c0, weights=None, loss="huber", tuning=Non
         _lib.check(lib.d4w_loc_robust_ws_bytes(nch, ncalls, ctypes.byref(nbytes)))
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=d) if nbytes.value else None
         if ncalls:                               # (an empty tensor has no pointer to hand over)
-            _lib.check(lib.d4w_loc_robust_f64(dev.ptr(cable), nch, dev.ptr(t), ncalls, dev.ptr(w) if w is not None else None, int(per_call),
-                                              float(c0), Nbiter, warmup, int(bool(fix_z)), code, tuning, scale,
-                                              dev.ptr(fg) if fg is not None else None, dev.out_ptr(hist) if Nbiter else None, dev.out_ptr(n),
-                                              dev.out_ptr(gtg), dev.out_ptr(ssr), dev.out_ptr(wsum), dev.out_ptr(nused), dev.out_ptr(sc),
-                                              dev.out_ptr(q) if q is not None else None, dev.out_ptr(r) if r is not None else None,
-                                              dev.out_ptr(ws) if ws is not None else None, dev.stream_ptr(t)))
+            _lib.check(lib.d4w_loc_robust_f64(dev.ptr(cable), nch, dev.ptr(t), ncalls, _p(w), int(per_call), float(c0), Nbiter, warmup,
+                                              int(bool(fix_z)), code, tuning, scale, _p(fg), dev.out_ptr(hist) if Nbiter else None,
+                                              dev.out_ptr(n), dev.out_ptr(gtg), dev.out_ptr(ssr), dev.out_ptr(wsum), dev.out_ptr(nused),
+                                              dev.out_ptr(sc), _p(q, True), _p(r, True), _p(ws, True), dev.stream_ptr(t)))
     if not return_stats:
         return _back(n, *given)
-    cnt = nused.cpu().numpy().astype(np.int64)
-    with np.errstate(all="ignore"):
-        var = np.where(cnt > p, ssr.cpu().numpy() / np.maximum(cnt - p, 1), np.nan)
-        cov = _covariance(np.where((cnt > 0)[:, None, None], gtg.cpu().numpy(), np.nan), var, quiet=True)
-        unc = np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
-    stats = {"variance": var, "covariance": cov, "uncertainty": unc, "nused": cnt}
-    stats = {k: _back(torch.from_numpy(np.ascontiguousarray(v)).to(d), *given) for k, v in stats.items()}
+    stats = _stats(gtg, ssr, nused, p, "nused", given)
     stats.update({k: _back(v, *given) for k, v in (("history", hist), ("scale", sc), ("robust_weights", q), ("residuals", r),
                                                     ("weight_sum", wsum))})
     return _back(n, *given), stats
@@ -1168,8 +1164,8 @@ def relocate(trace, fs, cable_pos, c0, n, length, max_lag, lead=0, rounds=1, ord
     and its Ti, coef and beam.  A CUDA float32 trace is read in place every round; a NumPy trace is uploaded by every call."""
     rounds = _whole(rounds, "rounds", 1)
     lead = _whole(lead, "lead", 0)
-    if isinstance(coef_power, bool) or _shape(coef_power) != () or not np.isfinite(coef_power) or coef_power < 0:
-        raise ValueError("coef_power must be a finite number >= 0, got %r" % (coef_power,))
+    if _number(coef_power, "coef_power") < 0:
+        raise ValueError("coef_power must not be negative, got %r" % (coef_power,))
     if _shape(n)[1:] != (4,) or len(_shape(n)) != 2:
         raise ValueError("n must be [ncalls x 4] = [x, y, z, t0] per call, got %s" % (_shape(n),))
     if not isinstance(loss, str) or loss not in _LOSSES:
@@ -1210,22 +1206,12 @@ def level_limits():
     return a.value, b.value, w.value
 
 
-def _level_check(a, start, length, noise_length, gap, delays):
-    """The arguments only received_levels has against the shared ones, on the host before any device work: (L, N, gap)."""
-    max_calls, max_length, _ = level_limits()
-    if a.ncalls > max_calls:
-        raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, max_calls))
-    ss = _shape(start)
-    if ss not in ((), (a.ncalls,)) or _dtype_name(start)[:3] not in ("int", "uin"):
-        raise ValueError("start must be an int or [ncalls] = (%d,) ints, got shape %s of %s" % (a.ncalls, ss, _dtype_name(start)))
-    L = _whole(length, "length", 1, max_length)
-    N = _whole(noise_length, "noise_length", 0, max_length)
-    gap = _whole(gap, "gap", 0, max_length)
-    if N + gap > max_length:
-        raise ValueError("noise_length + gap = %d is more than the %d one launch takes" % (N + gap, max_length))
-    if delays is not None and (_shape(delays) != (a.ncalls, a.nch) or _dtype_name(delays) != "int32"):
-        raise ValueError("delays must be int32 [ncalls x channel] = %s (beam_delays(rounded=True)), got %s %s"
-                         % ((a.ncalls, a.nch), _dtype_name(delays), _shape(delays)))
+def _level_check(a, length, noise_length, gap):
+    """The arguments only received_levels has, on the host before any device work: (L, N, gap)."""
+    L, N = _whole(length, "length", 1, a.max_length), _whole(noise_length, "noise_length", 0, a.max_length)
+    gap = _whole(gap, "gap", 0, a.max_length)
+    if N + gap > a.max_length:
+        raise ValueError("noise_length + gap = %d is more than the %d one launch takes" % (N + gap, a.max_length))
     return L, N, gap
 
 
@@ -1251,24 +1237,15 @@ def received_levels(trace, fs, cable_pos, c0, pos, start, length, noise_length=0
     bit-identical, independent of the other calls of the batch, of the alignment of a window and of where next_block begins;
     a scaling of trace by 2^k scales signal and noise by 4^k and peak by 2^k exactly.  A bad argument raises ValueError on the
     host before any device work.  NumPy in -> NumPy out; any tensor in -> tensors on that device and stream."""
-    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights)
-    L, N, gap = _level_check(a, start, length, noise_length, gap, delays)
-    _upload(a, like=(start, delays))
-    d = a.device
-    if dev.is_tensor(start):
-        s = start.to(d, torch.int64).reshape(-1)
-    else:
-        s = torch.from_numpy(np.array(start, dtype=np.int64).reshape(-1)).to(d)
-    s = s.expand(a.ncalls).contiguous()
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights, start=start,
+               table=(delays, "r"), limits=level_limits()[:2])
+    L, N, gap = _level_check(a, length, noise_length, gap)
+    d = _upload(a).device
     with torch.cuda.device(d):
         signal, noise, peak = (torch.empty((a.ncalls, a.nch), dtype=torch.float32, device=d) for _ in range(3))
         if a.ncalls:
-            r = _beam_delays(a, True) if delays is None else _given_table(delays, d)
-            nb, w = a.nb, a.w
-            _lib.check(_lib.lib.d4w_level_f32(dev.ptr(a.e), a.pitch, a.nch, a.ns, dev.ptr(nb) if nb is not None else None, a.pitch_nb,
-                                              nb.shape[1] if nb is not None else 0, dev.ptr(r), dev.ptr(s), a.ncalls, L, gap, N,
-                                              dev.ptr(w) if w is not None else None, dev.out_ptr(signal), dev.out_ptr(noise),
-                                              dev.out_ptr(peak), dev.stream_ptr(a.e)))
+            _lib.check(_lib.lib.d4w_level_f32(*_record(a), dev.ptr(a.kr), dev.ptr(a.s), a.ncalls, L, gap, N, _p(a.w), dev.out_ptr(signal),
+                                              dev.out_ptr(noise), dev.out_ptr(peak), dev.stream_ptr(a.e)))
     return tuple(_out(y, a.as_tensor) for y in (signal, noise, peak))
 
 
@@ -1359,73 +1336,47 @@ def project_limits():
     return a.value, b.value, w.value
 
 
-def _project_check(a, beam, start, order, delays, amp=_SKIP):
+def _project_check(a, beam, amp=_SKIP):
     """The arguments only project_calls and subtract_calls have against the shared ones, on the host before any device work:
-    (L, the given delay tables as a tuple)."""
-    max_calls, max_length, _ = project_limits()
-    if a.ncalls > max_calls:
-        raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, max_calls))
-    bs = _shape(beam)
-    if not ((len(bs) == 2 and bs[0] == a.ncalls) or (len(bs) == 1 and a.ncalls == 1)) or _dtype_name(beam) != "float32":
-        raise ValueError("beam must be float32 [ncalls x L] = (%d, L) (or [L] for one call), got %s %s" % (a.ncalls, _dtype_name(beam), bs))
-    if bs[-1] < 1 or bs[-1] > max_length:
-        raise ValueError("the beam length %d is outside 1 .. %d" % (bs[-1], max_length))
+    the beam's length."""
     if amp is not _SKIP:
         if _shape(amp) not in ((a.ncalls, a.nch),) + (((a.nch,),) if a.ncalls == 1 else ()) or _dtype_name(amp) != "float32":
             raise ValueError("amp must be float32 [ncalls x channel] = %s, got %s %s" % ((a.ncalls, a.nch), _dtype_name(amp), _shape(amp)))
-    return _beam_check(a, start, bs[-1], order, delays)
+    return _waveforms(beam, "beam", a)
 
 
-def _order(order):
-    if isinstance(order, bool) or order not in (0, 1, 3):
-        raise ValueError("order must be 0, 1 or 3, got %r" % (order,))
-    return int(order)
+def _check_inplace(inplace, trace, next_block):
+    """inplace=True writes into the callers' blocks: they must be what the kernels take as it is, on one device."""
+    if inplace and not (_inplace_view(trace) and (next_block is None or _inplace_view(next_block, trace.device))):
+        raise ValueError("inplace=True needs trace (and next_block) as CUDA float32 tensors with unit column stride on one device")
+    return bool(inplace)
 
 
-def _starts(start, a):
-    """start as int64 [ncalls] on the device."""
-    if dev.is_tensor(start):
-        s = start.to(a.device, torch.int64).reshape(-1)
-    else:
-        s = torch.from_numpy(np.array(start, dtype=np.int64).reshape(-1)).to(a.device)
-    return s.expand(a.ncalls).contiguous()
-
-
-def _tables(a, order, tables):
-    """(k or r, f or None) on the device: the given tables, or beam_delays' for the positions a.p."""
-    if tables:
-        return _given_table(tables[0], a.device), (_given_table(tables[1], a.device) if order else None)
-    return (_beam_delays(a, True), None) if order == 0 else _beam_delays(a, False)
-
-
-def _project(a, kr, f, b, s, order):
+def _project(a, b, order):
     """The fit on device tensors: (amp, coef) float32 [ncalls x nch]; no launch without a call."""
     amp, coef = (torch.empty((a.ncalls, a.nch), dtype=torch.float32, device=a.device) for _ in range(2))
     if a.ncalls:
-        nb, w = a.nb, a.w
-        _lib.check(_lib.lib.d4w_project_f32(dev.ptr(a.e), a.pitch, a.nch, a.ns, dev.ptr(nb) if nb is not None else None, a.pitch_nb,
-                                            nb.shape[1] if nb is not None else 0, dev.ptr(kr), dev.ptr(f) if f is not None else None, dev.ptr(b),
-                                            b.shape[1], dev.ptr(s), a.ncalls, order, dev.ptr(w) if w is not None else None, dev.out_ptr(amp),
-                                            dev.out_ptr(coef), dev.stream_ptr(a.e)))
+        _lib.check(_lib.lib.d4w_project_f32(*_record(a), dev.ptr(a.kr), _p(a.f), dev.ptr(b), b.shape[1], dev.ptr(a.s), a.ncalls, order, _p(a.w),
+                                            dev.out_ptr(amp), dev.out_ptr(coef), dev.stream_ptr(a.e)))
     return amp, coef
 
 
-def _subtract(a, kr, f, b, s, amp, order, inplace):
-    """The subtraction on device tensors: (y, ynext or None); in place y and ynext are a.e and a.nb themselves."""
-    nb = a.nb
+def _subtract(a, b, amp, order, inplace, trace, next_block):
+    """The subtraction on device tensors, and its result in the callers' container: the residual, or (residual, residual_next)
+    with a next block; in place these are trace and next_block themselves.  Without a call it still launches, with null call
+    pointers: out of place the copy has to be written."""
     if inplace:
-        y, yn, py, pyn = a.e, nb, a.pitch, a.pitch_nb
+        y, yn, py, pyn = a.e, a.nb, a.pitch, a.pitch_nb
     else:
         y = torch.empty((a.nch, a.ns), dtype=torch.float32, device=a.device)
-        yn = torch.empty((a.nch, nb.shape[1]), dtype=torch.float32, device=a.device) if nb is not None else None
-        py, pyn = a.ns, (nb.shape[1] if nb is not None else 0)
-    none = a.ncalls == 0
-    _lib.check(_lib.lib.d4w_project_subtract_f32(dev.ptr(a.e), a.pitch, a.nch, a.ns, dev.ptr(nb) if nb is not None else None, a.pitch_nb,
-                                                 nb.shape[1] if nb is not None else 0, None if none else dev.ptr(kr),
-                                                 dev.ptr(f) if f is not None and not none else None, None if none else dev.ptr(b),
-                                                 b.shape[1], None if none else dev.ptr(s), None if none else dev.ptr(amp), a.ncalls, order,
-                                                 dev.out_ptr(y), py, dev.out_ptr(yn) if yn is not None else None, pyn, dev.stream_ptr(a.e)))
-    return y, yn
+        yn = torch.empty((a.nch, a.ns_nb), dtype=torch.float32, device=a.device) if a.nb is not None else None
+        py, pyn = a.ns, a.ns_nb
+    kr, f, b_, s, amp = (_p(t) if a.ncalls else None for t in (a.kr, a.f, b, a.s, amp))
+    _lib.check(_lib.lib.d4w_project_subtract_f32(*_record(a), kr, f, b_, b.shape[1], s, amp, a.ncalls, order, dev.out_ptr(y), py, _p(yn, True),
+                                                 pyn, dev.stream_ptr(a.e)))
+    if inplace:
+        return trace if next_block is None else (trace, next_block)
+    return _out(y, a.as_tensor) if yn is None else (_out(y, a.as_tensor), _out(yn, a.as_tensor))
 
 
 def project_calls(trace, fs, cable_pos, c0, pos, beam, start, order=1, weights=None, next_block=None, *, delays=None):
@@ -1450,18 +1401,14 @@ def project_calls(trace, fs, cable_pos, c0, pos, beam, start, order=1, weights=N
     bit-identical, independent of the batch and of where next_block begins; a scaling of a channel by 2^k scales amp by 2^k
     exactly and keeps coef's bits.  A bad argument raises ValueError on the host before any device work.
     NumPy in -> NumPy out; any tensor in -> tensors on that device and stream."""
-    order = _order(order)
-    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights)
-    L, tables = _project_check(a, beam, start, order, delays)
-    _upload(a, like=(start, beam) + tables)
+    order, kind = _order(order)
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights, start=start,
+               table=(delays, kind), limits=project_limits()[:2])
+    L = _project_check(a, beam)
+    _upload(a, like=(beam,))
     with torch.cuda.device(a.device):
-        out = _project(a, *_tables(a, order, tables), _given_table(beam, a.device).reshape(a.ncalls, L), _starts(start, a), order)
+        out = _project(a, _given_table(beam, a.device).reshape(a.ncalls, L), order)
     return tuple(_out(y, a.as_tensor) for y in out)
-
-
-def _inplace_view(t):
-    return (dev.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
-            and (t.stride(0) >= t.shape[1] or t.shape[0] == 1))
 
 
 def subtract_calls(trace, fs, cable_pos, c0, pos, beam, start, amp, order=1, next_block=None, inplace=False, *, delays=None):
@@ -1479,18 +1426,14 @@ def subtract_calls(trace, fs, cable_pos, c0, pos, beam, start, amp, order=1, nex
     beam, start, order, delays: as for project_calls; amp: float32 [ncalls x channel] (or [channel] for one call).
     A gather without atomics: run-to-run bit-identical.  A bad argument raises ValueError on the host before any device work.
     NumPy in -> NumPy out; any tensor in -> tensors on that device and stream."""
-    order = _order(order)
-    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block)
-    L, tables = _project_check(a, beam, start, order, delays, amp)
-    if inplace and not (_inplace_view(trace) and (next_block is None or (_inplace_view(next_block) and next_block.device == trace.device))):
-        raise ValueError("inplace=True needs trace (and next_block) as CUDA float32 tensors with unit column stride on one device")
-    _upload(a, like=(start, beam, amp) + tables)
+    order, kind = _order(order)
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, start=start, table=(delays, kind),
+               limits=project_limits()[:2])
+    L, inplace = _project_check(a, beam, amp), _check_inplace(inplace, trace, next_block)
+    _upload(a, like=(beam, amp))
     with torch.cuda.device(a.device):
-        y, yn = _subtract(a, *_tables(a, order, tables), _given_table(beam, a.device).reshape(a.ncalls, L), _starts(start, a),
-                          _given_table(amp, a.device).reshape(a.ncalls, a.nch), order, bool(inplace))
-    if inplace:
-        return trace if next_block is None else (trace, next_block)
-    return _out(y, a.as_tensor) if yn is None else (_out(y, a.as_tensor), _out(yn, a.as_tensor))
+        return _subtract(a, _given_table(beam, a.device).reshape(a.ncalls, L), _given_table(amp, a.device).reshape(a.ncalls, a.nch), order,
+                         inplace, trace, next_block)
 
 
 def remove_calls(trace, fs, cable_pos, c0, pos, start, length, order=1, min_coef=0.0, weights=None, next_block=None, inplace=False,
@@ -1506,30 +1449,18 @@ def remove_calls(trace, fs, cable_pos, c0, pos, start, length, order=1, min_coef
     time on a channel are not fitted jointly, so the louder one belongs first and a second remove_calls over the residual
     refines the weaker.  The beam holds 1 / channels of every channel's own noise (see project_calls), which this
     subtracts along with the call.  Arguments as for beamform and subtract_calls; length is the beam's, in samples."""
-    order = _order(order)
-    if min_coef is not None and (isinstance(min_coef, bool) or _shape(min_coef) != () or not np.isfinite(min_coef)):
-        raise ValueError("min_coef must be None or a finite number, got %r" % (min_coef,))
-    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights)
-    if a.ncalls > project_limits()[0]:
-        raise ValueError("%d calls are more than the %d one launch takes" % (a.ncalls, project_limits()[0]))
-    L = _whole(length, "length", 1, project_limits()[1])
-    _beam_check(a, start, L, order, None)
-    if inplace and not (_inplace_view(trace) and (next_block is None or (_inplace_view(next_block) and next_block.device == trace.device))):
-        raise ValueError("inplace=True needs trace (and next_block) as CUDA float32 tensors with unit column stride on one device")
-    _upload(a, like=(start,))
+    order, kind = _order(order)
+    min_coef = None if min_coef is None else _number(min_coef, "min_coef")
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights, start=start,
+               table=(None, kind), limits=tuple(map(min, beam_limits()[:2], project_limits()[:2])))      # the beam's and the fit's
+    L, inplace = _whole(length, "length", 1, a.max_length), _check_inplace(inplace, trace, next_block)
+    _upload(a)
     with torch.cuda.device(a.device):
-        s = _starts(start, a)
-        kr, f = _tables(a, order, ())
-        beam = _beam(a, kr, f, s, L, order, True)
-        amp, coef = _project(a, kr, f, beam, s, order)
+        beam = _beam(a, L, order, True)
+        amp, coef = _project(a, beam, order)
         if min_coef is not None:
-            amp = torch.where(coef < float(min_coef), torch.full((), float("nan"), dtype=torch.float32, device=a.device), amp)
-        y, yn = _subtract(a, kr, f, beam, s, amp, order, bool(inplace))
-    if inplace:
-        res = (trace,) if next_block is None else (trace, next_block)
-    else:
-        res = (_out(y, a.as_tensor),) if yn is None else (_out(y, a.as_tensor), _out(yn, a.as_tensor))
-    res = res[0] if len(res) == 1 else res
+            amp = torch.where(coef < min_coef, torch.full((), float("nan"), dtype=torch.float32, device=a.device), amp)
+        res = _subtract(a, beam, amp, order, inplace, trace, next_block)
     if not return_parts:
         return res
     parts = tuple(_out(t, a.as_tensor) for t in (beam, amp, coef))

@@ -141,6 +141,34 @@ def test_delays_given_against_built_inside_and_containers(dw, W):
     assert ka.same(f64[0], inside[0])
 
 
+def test_a_tensor_start_with_a_numpy_trace_and_views_across_the_seam(dw):
+    """The smallest record that can still go wrong: 5 channels, 64 samples, a next block of 9, two calls with a start each, the
+    second call's windows across the seam and partly off the end.  With NumPy arrays, with NumPy blocks and a tensor start (any
+    tensor in -> tensors out), and with column-sliced CUDA views throughout: the same bits, and within the derived tolerance of
+    the float64 restatement."""
+    nch, ns, ns2, L, M, fs = 5, 64, 9, 10, 2, 200.0
+    rng = np.random.default_rng(15)
+    cable = np.stack([30.0 * np.arange(nch), np.zeros(nch), np.full(nch, -20.0)], axis=1)       # moveouts of 6 .. 16 samples
+    pos = np.array([[10.0, 40.0, -5.0], [100.0, -60.0, -5.0]])
+    buf, nbuf = rng.standard_normal((nch, ns + 3)).astype(np.float32), rng.standard_normal((nch, ns2 + 2)).astype(np.float32)
+    x, nb = buf[:, :ns], nbuf[:, :ns2]
+    t = rng.standard_normal((2, L)).astype(np.float32)
+    r = dw.loc.beam_delays(cable, C0, fs, pos, rounded=True)
+    start = np.array([20, ns - 8], dtype=np.int64) - np.median(r, axis=1).astype(np.int64)
+    ref = ka.align_ref(x, t, r, start, M, None, nb)
+    q = np.array(ref.n0.tolist(), dtype=np.int64)[:, :, None] + np.arange(-M, M + 1)
+    assert ref.valid[0].all() and not ref.valid[1].all() and (ref.valid & (q < ns) & (q + L > ns)).any()      # a window across the seam
+    host = dw.loc.refine_arrivals(x, fs, cable, C0, pos, t, start, M, -1.0, next_block=nb, return_all=True)
+    assert all(isinstance(o, np.ndarray) for o in host) and ka.worst_ratio(host[3], ref) <= 1.0
+    ac.check_picks(host, ref.n0, M, fs, -1.0)
+    mixed = dw.loc.refine_arrivals(x, fs, cable, C0, pos, t, cuda(start), M, -1.0, next_block=nb, return_all=True)
+    views = dw.loc.refine_arrivals(cuda(buf)[:, :ns], fs, cable, C0, cuda(pos), cuda(t), cuda(start), M, -1.0, next_block=cuda(nbuf)[:, :ns2],
+                                   return_all=True, delays=cuda(r))
+    for out in (mixed, views):
+        assert all(isinstance(o, torch.Tensor) and o.is_cuda for o in out)
+        assert all(ka.same(o.cpu().numpy(), h) for o, h in zip(out, host))
+
+
 def test_bad_arguments(dw):
     nch, ns, L = 5, 64, 8
     base = dict(trace=np.ones((nch, ns), dtype=np.float32), fs=50.0, cable_pos=make_cable("line", nch), c0=C0, pos=np.zeros((2, 3)),

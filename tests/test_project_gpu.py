@@ -185,6 +185,45 @@ def test_more_than_one_tile_and_the_callers_stream(dw, W):
     assert kp.same(np.concatenate([h.cpu().numpy() for h in halves], axis=1), np.concatenate(out, axis=1))
 
 
+def test_remove_calls_across_the_seam_in_both_containers(dw):
+    """remove_calls on the smallest record that can still go wrong: 5 channels, 64 samples, a next block of 9, two calls with
+    a start each, the second call's supports across the seam (and one of them off the end of the record).  Once with NumPy
+    arrays and once with column-sliced CUDA views and a tensor start: the same bits in both containers, out of place and in
+    place, and the beam, the fit and the residual within the derived bounds of the float64 restatement, carried through the
+    chain as in test_end_to_end_remove_the_loud_call.  min_coef=None: no amplitude is masked."""
+    nch, ns, ns2, L, order = 5, 64, 9, 12, 1
+    rng = np.random.default_rng(5)
+    cable = np.stack([30.0 * np.arange(nch), np.zeros(nch), np.full(nch, -20.0)], axis=1)       # moveouts of 6 .. 16 samples
+    pos = np.array([[10.0, 40.0, -5.0], [100.0, -60.0, -5.0]])
+    buf, nbuf = rng.standard_normal((nch, ns + 3)).astype(np.float32), rng.standard_normal((nch, ns2 + 2)).astype(np.float32)
+    x, nb = buf[:, :ns], nbuf[:, :ns2]
+    delays = dw.loc.beam_delays(cable, C0, FS, pos)
+    start = np.array([20, ns - 8], dtype=np.int64) - np.median(delays[0], axis=1).astype(np.int64)
+    # the float64 restatement of the chain
+    beam_r, tol_b, _, _ = kb.beam_ref(x, delays, order, start, L, None, True, nb)
+    fit = kp.fit_ref(x, delays, order, start, beam_r, None, nb)
+    assert fit.valid[0].all() and fit.valid[1].any() and not fit.valid[1].all()
+    assert (fit.valid & (fit.lo < ns) & (fit.lo + fit.W > ns)).any()                            # a support across the seam
+    dfit = kp.fit_ref(x, delays, order, start, beam_r, None, nb, beam_tol=tol_b)
+    y, tol_y, reached = kp.subtract_ref(x, delays, order, start, beam_r, fit.amp, nb, amp_tol=dfit.tol_amp, beam_tol=tol_b)
+    # NumPy in, NumPy out
+    got = dw.loc.remove_calls(x, FS, cable, C0, pos, start, L, order, None, next_block=nb, return_parts=True)
+    assert len(got) == 5 and all(isinstance(o, np.ndarray) and o.dtype == np.float32 for o in got)
+    res, res2, beam, amp, coef = got
+    rb, rf = kb.worst_ratio(beam, beam_r, tol_b), kp.worst_fit((amp, coef), dfit)
+    ry = kp.worst_subtract(np.concatenate([res, res2], axis=1), y, tol_y, reached, np.concatenate([x, nb], axis=1))
+    print("device / bound: beam %.3g, fit %.3g, residual %.3g" % (rb, rf, ry))
+    assert rb <= 1.0 and rf <= 1.0 and ry <= 1.0
+    # column-sliced CUDA views and a tensor start: tensors on the device with the same bits
+    xt, nt = cuda(buf)[:, :ns], cuda(nbuf)[:, :ns2]
+    gt = dw.loc.remove_calls(xt, FS, cable, C0, pos, cuda(start), L, order, None, next_block=nt, return_parts=True)
+    assert all(isinstance(o, torch.Tensor) and o.is_cuda for o in gt) and all(kp.same(host(a), b) for a, b in zip(gt, got))
+    assert kp.same(host(xt._base), buf) and kp.same(host(nt._base), nbuf)                       # out of place: the views keep their bits
+    out = dw.loc.remove_calls(xt, FS, cable, C0, pos, cuda(start), L, order, None, next_block=nt, inplace=True)
+    assert out[0] is xt and out[1] is nt and kp.same(host(xt), res) and kp.same(host(nt), res2)
+    assert kp.same(host(xt._base)[:, ns:], buf[:, ns:]) and kp.same(host(nt._base)[:, ns2:], nbuf[:, ns2:])      # the padding too
+
+
 # ---- end to end --------------------------------------------------------------------------------------------------------------
 def sweep(n=200):
     """A Hann-windowed 25 -> 15 Hz sweep of n samples at FS."""

@@ -66,7 +66,9 @@ BAD = [dict(order=2), dict(order=-1), dict(order=1.5), dict(order=True), dict(le
        dict(delays=(np.zeros((2, 5), dtype=np.int32), np.zeros((2, 5), dtype=np.float64))),
        dict(delays=(np.zeros((2, 5), dtype=np.int64), np.zeros((2, 5), dtype=np.float32))), dict(delays=(np.zeros((2, 5), dtype=np.int32),)),
        dict(order=0, delays=np.zeros((2, 5), dtype=np.float32)), dict(order=0, delays=np.zeros((2, 4), dtype=np.int32)),
-       dict(pos=np.zeros((65536 * 2, 3)))]
+       dict(pos=np.zeros((65536 * 2, 3))),
+       # length goes through the one whole-number check of the module: no infinity, no array, no bool
+       dict(length=float("inf")), dict(length=np.ones(2)), dict(length=True)]
 
 
 @pytest.mark.parametrize("kw", BAD, ids=lambda kw: "-".join("%s" % k for k in kw))

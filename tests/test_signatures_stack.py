@@ -68,7 +68,10 @@ BAD = ([("stack_grid", kw) for kw in BAD_STACK + [dict(delays=np.zeros((1, 2, 4)
        + [("delay_table", kw) for kw in BAD_GRID]
        + [("arrivals_near", kw) for kw in BAD_GEOMETRY + [dict(halfwidth=-1), dict(pos=np.zeros((2, 2))), dict(t0=np.zeros(3)),
                                                            dict(threshold=np.zeros(4)), dict(weights=np.ones(4)),
-                                                           dict(env=np.ones((4, 64), dtype=np.float32)), dict(env=np.ones(64))]])
+                                                           dict(env=np.ones((4, 64), dtype=np.float32)), dict(env=np.ones(64))]]
+       # halfwidth and max_calls go through the one whole-number check of the module (appended: the ids above keep their numbers)
+       + [("locate_stack", dict(halfwidth=1.5)), ("locate_stack", dict(max_calls=2.5)), ("locate_stack", dict(halfwidth=True)),
+          ("arrivals_near", dict(halfwidth=2.5)), ("arrivals_near", dict(halfwidth=True))])
 BASE = {
     "stack_grid": dict(GEOMETRY, env=ENV, **GRID),
     "locate_stack": dict(GEOMETRY, env=ENV, threshold=1.0, halfwidth=3, pick_threshold=0.5, **GRID),
