@@ -165,6 +165,13 @@ def _load():
         "d4w_stft_mag_mm_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
         "d4w_scale_rows_f32": (c_int, [c_void_p, c_int, ctypes.c_size_t, c_void_p, c_int, c_void_p]),
         "d4w_row_median_f32": (c_int, [c_void_p, c_int, ctypes.c_size_t, c_void_p, c_void_p]),
+        "d4w_row_quantile_f32": (c_int, [c_void_p, c_int, ctypes.c_size_t, ctypes.c_size_t, P(ctypes.c_double), c_int, c_void_p, c_void_p]),
+        "d4w_row_quantile_limits": (c_int, [P(c_int)]),
+        "d4w_channel_noise_fits_lds": (c_int, [c_int]),
+        "d4w_channel_noise_ws_bytes": (ctypes.c_size_t, [c_int, c_int]),
+        "d4w_channel_noise_f32": (c_int, [c_void_p, c_int, c_int, ctypes.c_size_t, P(ctypes.c_double), c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+        "d4w_find_peaks_rowthr_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, ctypes.c_double, c_void_p, c_void_p, c_int, c_void_p]),
         "d4w_spectrocorr_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
                                         c_int, c_void_p, c_void_p]),
         "d4w_find_peaks_f32": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_int, c_void_p]),

@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "fft_host.h"
+#include "row_select.h"
 
 namespace d4w {
 
@@ -185,6 +186,44 @@ __device__ __forceinline__ float an_ifreq(float2 z0, float2 z1, float fscale) {
     return atan2f(p.y, p.x) * fscale;
 }
 
+// The Hilbert multiplier on the transformed row (see above): the packed form untangles the real spectrum, applies -i / +i and
+// tangles again for the packed inverse; the plain form scales by scipy's h.
+template <bool PACKED>
+__device__ __forceinline__ void an_multiplier(float2* tile, const RowFftDev& F, int tid, int nthr) {
+    const int L = F.ax.L;
+    if (PACKED) {
+        const int M = L;
+        for (int f = tid; f <= M / 2; f += nthr) {
+            const int g = (f == 0) ? 0 : M - f;
+            const int pa = F.pos[f], pb = F.pos[g];
+            const float2 a = tile[pa], bc = c_conj(tile[pb]);
+            float2 out_a = make_float2(0.f, 0.f), out_b = make_float2(0.f, 0.f);
+            if (f != 0) {
+                const float2 w = F.wpack[f];
+                const float2 E = c_scale(c_add(a, bc), 0.5f);
+                const float2 O = c_mul_mi(c_scale(c_sub(a, bc), 0.5f));
+                const float2 tO = c_mul(w, O);
+                const float2 Yp = c_mul_mi(c_add(E, tO));             // -i X(f)
+                const float2 Ym = c_mul_pi(c_sub(E, tO));             // +i X(f + M)  (negative frequency)
+                const float2 S = c_scale(c_add(Yp, Ym), 0.5f);
+                const float2 D = c_mul_pi(c_mulc(c_scale(c_sub(Yp, Ym), 0.5f), w));
+                out_a = c_add(S, D);
+                out_b = c_conj(c_sub(S, D));
+            }
+            tile[pa] = out_a;
+            if (pb != pa) tile[pb] = out_b;
+        }
+    } else {
+        const int half = (L + 1) / 2;                                 // first negative frequency
+        for (int p = tid; p < L; p += nthr) {
+            const int f = F.p2f[p];
+            float h = (f < half) ? 2.f : 0.f;
+            if (f == 0 || (2 * f == L)) h = 1.f;
+            tile[p] = c_scale(tile[p], h);
+        }
+    }
+}
+
 constexpr int kAnMaxThreads = 512;
 template <bool PACKED, bool GENERIC>
 __global__ __launch_bounds__(kAnMaxThreads) void analytic_rows(RowFftDev F, const float* __restrict__ x, int ns,
@@ -217,37 +256,7 @@ __global__ __launch_bounds__(kAnMaxThreads) void analytic_rows(RowFftDev F, cons
     }
     lds_barrier();
     row_dft<false, GENERIC>(tile, F, tw, tid, nthr);
-    if (PACKED) {
-        const int M = L;
-        for (int f = tid; f <= M / 2; f += nthr) {
-            const int g = (f == 0) ? 0 : M - f;
-            const int pa = F.pos[f], pb = F.pos[g];
-            const float2 a = tile[pa], bc = c_conj(tile[pb]);
-            float2 out_a = make_float2(0.f, 0.f), out_b = make_float2(0.f, 0.f);
-            if (f != 0) {
-                const float2 w = F.wpack[f];
-                const float2 E = c_scale(c_add(a, bc), 0.5f);
-                const float2 O = c_mul_mi(c_scale(c_sub(a, bc), 0.5f));
-                const float2 tO = c_mul(w, O);
-                const float2 Yp = c_mul_mi(c_add(E, tO));             // -i X(f)
-                const float2 Ym = c_mul_pi(c_sub(E, tO));             // +i X(f + M)  (negative frequency)
-                const float2 S = c_scale(c_add(Yp, Ym), 0.5f);
-                const float2 D = c_mul_pi(c_mulc(c_scale(c_sub(Yp, Ym), 0.5f), w));
-                out_a = c_add(S, D);
-                out_b = c_conj(c_sub(S, D));
-            }
-            tile[pa] = out_a;
-            if (pb != pa) tile[pb] = out_b;
-        }
-    } else {
-        const int half = (L + 1) / 2;                                 // first negative frequency
-        for (int p = tid; p < L; p += nthr) {
-            const int f = F.p2f[p];
-            float h = (f < half) ? 2.f : 0.f;
-            if (f == 0 || (2 * f == L)) h = 1.f;
-            tile[p] = c_scale(tile[p], h);
-        }
-    }
+    an_multiplier<PACKED>(tile, F, tid, nthr);
     lds_barrier();
     row_dft<true, GENERIC>(tile, F, tw, tid, nthr);
     const float scale = 1.0f / (float)L;
@@ -739,6 +748,196 @@ __global__ __launch_bounds__(kSpThreads) void row_median(const float* __restrict
         }
         med[blockIdx.x] = (n & 1) ? med_unkey(a) : 0.5f * (med_unkey(a) + med_unkey(b));
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// np.quantile of every row (row_select.h) and the noise floor of every channel -- reference scripts/main_bathynoise.py:139,
+// 183-194 (median and mean of |hilbert|, std, per channel) and :256-259 (mean square and mean envelope of a quiet window).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kSpThreads) void row_quantile(const float* __restrict__ v, size_t n, size_t ld, SelRanks R,
+                                                           float* __restrict__ out, float* __restrict__ mean) {
+    __shared__ double sel_raw[kSelLdsBytes / sizeof(double)];
+    const SelLds S = sel_lds(reinterpret_cast<unsigned char*>(sel_raw));
+    double sum = 0.0;
+    row_select(v + (size_t)blockIdx.x * ld, n, R, S, threadIdx.x, kSpThreads, out ? out + (size_t)blockIdx.x * R.nq : nullptr,
+               mean ? &sum : nullptr);
+    if (mean && threadIdx.x == 0) mean[blockIdx.x] = (float)(sum / (double)n);
+}
+
+// mean(x^2) and np.std(x) of a row: every lane keeps sum x^2 and, shifted by the first sample it meets, sum d and sum d^2 in
+// float64 (row_var's form); the lanes' (count, mean, M2) are merged pairwise, x^2 summed by the same butterfly.
+// Three float64 operations per sample (they are what the one-read kernel pays for its moments): the lane's sum of squares
+// follows from the shifted sums, sum x^2 = sum d^2 + 2 c sum d + n c^2.
+struct MomLane { double c, s1, s2; unsigned cnt; };
+__device__ __forceinline__ void mom_take(MomLane& a, float v) {
+    const double d = (double)v - a.c;
+    a.s1 += d;
+    a.s2 = fma(d, d, a.s2);
+    a.cnt += 1u;
+}
+// red: [4][kAnMaxThreads / 64] doubles of LDS.  One barrier; thread 0 writes.
+__device__ __forceinline__ void mom_finish(const MomLane& l, double (*red)[kAnMaxThreads / 64], int tid, int nthr, int ns,
+                                           float* __restrict__ mean_sq, float* __restrict__ sd) {
+    const double cnt = (double)l.cnt;
+    double m2 = l.cnt ? l.s2 - l.s1 * l.s1 / cnt : 0.0;
+    if (m2 < 0.0) m2 = 0.0;                                        // (a NaN stays one)
+    VarAcc a{cnt, l.cnt ? l.c + l.s1 / cnt : 0.0, m2};
+    double sq = l.cnt ? l.s2 + 2.0 * l.c * l.s1 + cnt * l.c * l.c : 0.0;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        a = var_merge(a, VarAcc{__shfl_xor(a.n, off), __shfl_xor(a.mean, off), __shfl_xor(a.m2, off)});
+        sq += __shfl_xor(sq, off);
+    }
+    if ((tid & 63) == 0) { red[0][tid / 64] = a.n; red[1][tid / 64] = a.mean; red[2][tid / 64] = a.m2; red[3][tid / 64] = sq; }
+    __syncthreads();
+    if (tid == 0) {
+        VarAcc t{red[0][0], red[1][0], red[2][0]};
+        double q = red[3][0];
+        for (int w = 1; w < nthr / 64; ++w) {
+            t = var_merge(t, VarAcc{red[0][w], red[1][w], red[2][w]});
+            q += red[3][w];
+        }
+        if (mean_sq) mean_sq[blockIdx.x] = (float)(q / (double)ns);
+        if (sd) sd[blockIdx.x] = (float)sqrt(t.m2 / (double)ns);
+    }
+}
+
+__global__ __launch_bounds__(kSpThreads) void row_moments(const float* __restrict__ x, int ns, size_t ld,
+                                                          float* __restrict__ mean_sq, float* __restrict__ sd) {
+    __shared__ double red[4][kAnMaxThreads / 64];
+    const float* row = x + (size_t)blockIdx.x * ld;
+    const int tid = threadIdx.x;
+    MomLane a{0.0, 0.0, 0.0, 0u};
+    if ((ns & 3) == 0 && (reinterpret_cast<uintptr_t>(row) & 15) == 0) {
+        const float4* r4 = reinterpret_cast<const float4*>(row);
+        const int n4 = ns >> 2;
+        if (tid < n4) a.c = (double)r4[tid].x;
+        constexpr int kAhead = 4;
+        for (int i0 = tid; i0 < n4; i0 += kAhead * kSpThreads) {
+            float4 q[kAhead];
+#pragma unroll
+            for (int k = 0; k < kAhead; ++k) {
+                const int i = i0 + k * kSpThreads;
+                if (i < n4) q[k] = r4[i];
+            }
+#pragma unroll
+            for (int k = 0; k < kAhead; ++k)
+                if (i0 + k * kSpThreads < n4) { mom_take(a, q[k].x); mom_take(a, q[k].y); mom_take(a, q[k].z); mom_take(a, q[k].w); }
+        }
+    } else {
+        if (tid < ns) a.c = (double)row[tid];
+        for (int i = tid; i < ns; i += kSpThreads) mom_take(a, row[i]);
+    }
+    mom_finish(a, red, tid, kSpThreads, ns, mean_sq, sd);
+}
+
+// rows of a column window gathered into contiguous rows (the long-row transform reads whole rows)
+__global__ __launch_bounds__(kSpThreads) void gather_rows(const float* __restrict__ x, int ns, size_t ld, float* __restrict__ y) {
+    const float* row = x + (size_t)blockIdx.y * ld;
+    float* out = y + (size_t)blockIdx.y * ns;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += gridDim.x * blockDim.x) out[i] = row[i];
+}
+
+// The one-read form: one workgroup per row stages the row (taking the moments of the samples as they pass), runs analytic_rows'
+// transform - multiplier - inverse, leaves the ENVELOPE in the tile in place of the Hilbert values and runs the select and the
+// envelope's sum over it in LDS; nothing of [nx, ns] size is written.  The second touch of the samples (the envelope's real
+// part, as in analytic_rows) re-reads the row this workgroup has just staged.
+//   PACKED: even ns, the tile holds ns / 2 pairs of Hilbert values, replaced pair by pair by the same lane.  al8 = 0 (a column
+//     window whose rows are only 4-byte aligned): the pairs are read as two 4-byte loads, never as one 8-byte load.
+//   plain (odd ns): the tile holds ns complex values and the envelope takes the first half of it; a chunk of envelopes is
+//     formed, a barrier, then written -- chunk k lands on complex elements [k nthr / 2, (k + 1) nthr / 2), all read by then.
+//   sel_off: where the select's scratch lies -- in the tile's unused part where that is large enough, else behind the twiddles.
+template <bool PACKED, bool GENERIC>
+__global__ __launch_bounds__(kAnMaxThreads) void noise_rows(RowFftDev F, const float* __restrict__ x, int ns, size_t ld,
+                                                         int al8, int sel_off, SelRanks R, float* __restrict__ mean_sq,
+                                                         float* __restrict__ sd, float* __restrict__ env_mean,
+                                                         float* __restrict__ env_q) {
+    D4W_DYN_LDS(smem_raw);
+    __shared__ double red[4][kAnMaxThreads / 64];
+    float2* tile = reinterpret_cast<float2*>(smem_raw);
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int L = F.ax.L;
+    const float* xr = x + (size_t)blockIdx.x * ld;
+    const bool want_env = env_mean || R.nq > 0;                      // uniform
+    TwLds tw{};
+    if (want_env) tw = tw_stage(row_tw_axis(F), tile + row_tile_elems(F), tid, nthr);
+    MomLane a{0.0, 0.0, 0.0, 0u};
+    auto pair_at = [&](int m) -> float2 {
+        if (al8) return reinterpret_cast<const float2*>(xr)[m];
+        return make_float2(xr[2 * m], xr[2 * m + 1]);
+    };
+    constexpr int kAhead = 8;
+    if (PACKED) {
+        if (tid < L) a.c = (double)xr[2 * tid];
+        for (int m0 = tid; m0 < L; m0 += kAhead * nthr) {
+            float2 q[kAhead];
+#pragma unroll
+            for (int k = 0; k < kAhead; ++k) {
+                const int m = m0 + k * nthr;
+                q[k] = (m < L) ? pair_at(m) : make_float2(0.f, 0.f);
+            }
+#pragma unroll
+            for (int k = 0; k < kAhead; ++k) {
+                const int m = m0 + k * nthr;
+                if (m < L) {
+                    if (want_env) tile[m] = q[k];
+                    mom_take(a, q[k].x);
+                    mom_take(a, q[k].y);
+                }
+            }
+        }
+    } else {
+        if (tid < L) a.c = (double)xr[tid];
+        for (int n = tid; n < L; n += nthr) {
+            const float v = xr[n];
+            if (want_env) tile[n] = make_float2(v, 0.f);
+            mom_take(a, v);
+        }
+    }
+    mom_finish(a, red, tid, nthr, ns, mean_sq, sd);
+    if (!want_env) return;
+    lds_barrier();
+    row_dft<false, GENERIC>(tile, F, tw, tid, nthr);
+    an_multiplier<PACKED>(tile, F, tid, nthr);
+    lds_barrier();
+    row_dft<true, GENERIC>(tile, F, tw, tid, nthr);
+    const float scale = 1.0f / (float)L;
+    float* env = reinterpret_cast<float*>(tile);
+    if (PACKED) {
+        for (int m0 = tid; m0 < L; m0 += kAhead * nthr) {
+            float2 q[kAhead];
+#pragma unroll
+            for (int k = 0; k < kAhead; ++k) {
+                const int m = m0 + k * nthr;
+                q[k] = (m < L) ? pair_at(m) : make_float2(0.f, 0.f);
+            }
+#pragma unroll
+            for (int k = 0; k < kAhead; ++k) {
+                const int m = m0 + k * nthr;
+                if (m < L) {
+                    const float2 h = tile[m];
+                    const float i0 = h.x * scale, i1 = h.y * scale;
+                    tile[m] = make_float2(sqrtf(fmaf(q[k].x, q[k].x, i0 * i0)), sqrtf(fmaf(q[k].y, q[k].y, i1 * i1)));
+                }
+            }
+        }
+    } else {
+        for (int i0 = 0; i0 < ns; i0 += nthr) {
+            const int i = i0 + tid;
+            float v = 0.f;
+            if (i < ns) {
+                const float re = xr[i], im = tile[i].y * scale;
+                v = sqrtf(fmaf(re, re, im * im));
+            }
+            lds_barrier();
+            if (i < ns) env[i] = v;
+        }
+    }
+    lds_barrier();
+    const SelLds S = sel_lds(smem_raw + sel_off);
+    double sum = 0.0;
+    row_select(env, (size_t)ns, R, S, tid, nthr, env_q ? env_q + (size_t)blockIdx.x * R.nq : nullptr, env_mean ? &sum : nullptr);
+    if (env_mean && tid == 0) env_mean[blockIdx.x] = (float)(sum / (double)ns);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1612,10 +1811,15 @@ template <bool STAGED>
 __global__ __launch_bounds__(kFpThreads) void find_peaks_prom(const float* __restrict__ x, int ns, double thr0,
                                                               int bshift, int* __restrict__ idx,
                                                               int* __restrict__ counts, int cap,
-                                                              const float* __restrict__ thr_dev) {
+                                                              const float* __restrict__ thr_dev, int thr_rows) {
     // thr_dev: the threshold is thr0 x a DEVICE value (d4w_find_peaks_dthr_f32: "0.45 of the largest correlation" without the
     // host waiting for that maximum), formed in float64 like the host's 0.45 * float(c.max())
-    const double thr = thr_dev ? thr0 * (double)*thr_dev : thr0;
+    // thr_rows: one value per row (d4w_find_peaks_rowthr_f32: "k times this channel's noise floor")
+    const double thr = thr_dev ? thr0 * (double)thr_dev[thr_rows ? blockIdx.x : 0] : thr0;
+    if (thr_rows && !(thr == thr)) {                           // a NaN bar: no prominence is >= NaN (SciPy returns no peak)
+        if (threadIdx.x == 0) counts[blockIdx.x] = 0;
+        return;
+    }
     D4W_DYN_LDS(smem_raw);
     __shared__ int wave_tot[kFpThreads / 64 + 2];              // + the candidate and hot-block counters of fp_scan
     __shared__ unsigned cfail[kFpList / 32];
@@ -1917,6 +2121,133 @@ int d4w_row_median_f32(const float* v, int nx, size_t per_row, float* med, void*
     return D4W_OK;
 }
 
+int d4w_row_quantile_limits(int* max_q) {
+    if (!max_q) return fail(D4W_EINVAL, "NULL argument");
+    *max_q = kSelMaxQ;
+    return D4W_OK;
+}
+
+// h = q (n - 1) in float64 like NumPy's virtual index; lo = floor(h), g = h - lo
+static int sel_ranks(const double* q_host, int nq, size_t n, SelRanks* R) {
+    if (nq < 0 || nq > kSelMaxQ) return fail(D4W_EINVAL, "nq = %d not in 0..%d", nq, kSelMaxQ);
+    if (nq && !q_host) return fail(D4W_EINVAL, "NULL argument");
+    memset(R, 0, sizeof(*R));
+    R->nq = nq;
+    for (int j = 0; j < nq; ++j) {
+        const double q = q_host[j];
+        if (!(q >= 0.0 && q <= 1.0)) return fail(D4W_EINVAL, "q[%d] = %g not in [0, 1]", j, q);
+        const double h = (double)(n - 1) * q;
+        double lo = floor(h);
+        if (lo >= (double)(n - 1)) lo = (double)(n - 1);
+        R->lo[j] = (unsigned)lo;
+        R->g[j] = h - lo;
+    }
+    return D4W_OK;
+}
+
+int d4w_row_quantile_f32(const float* v, int nx, size_t per_row, size_t ld, const double* q_host, int nq, float* out,
+                         void* stream) {
+    if (!v || !out || nx < 1) return fail(D4W_EINVAL, "bad argument");
+    if (per_row < 1 || per_row > 0x7FFFFFFFu || ld < per_row) return fail(D4W_EINVAL, "per_row = %zu (1 .. 2^31 - 1), ld = %zu >= per_row", per_row, ld);
+    if (nq < 1) return fail(D4W_EINVAL, "nq = %d not in 1..%d", nq, kSelMaxQ);
+    SelRanks R;
+    int rc = sel_ranks(q_host, nq, per_row, &R);
+    if (rc) return rc;
+    D4W_LAUNCH(row_quantile, dim3(nx), dim3(kSpThreads), 0, stream, v, per_row, ld, R, out, (float*)nullptr);
+    return D4W_OK;
+}
+
+// LDS of the one-read form for rows of ns samples (host arithmetic only): the transform tile and its twiddles as in
+// d4w_analytic_row_fits_lds, plus the select's scratch unless the tile's part the envelope leaves free holds it.
+static size_t noise_lds(int ns, size_t tile_bytes, int tile_elems, int* sel_off) {
+    const size_t env_bytes = ((size_t)ns * sizeof(float) + 7) & ~(size_t)7;
+    const size_t room = (size_t)tile_elems * sizeof(float2) - env_bytes;
+    if (room >= kSelLdsBytes) { *sel_off = (int)env_bytes; return tile_bytes; }
+    *sel_off = (int)tile_bytes;
+    return tile_bytes + kSelLdsBytes;
+}
+
+int d4w_channel_noise_fits_lds(int ns) {
+    if (ns < 2) return 0;
+    int L = (ns % 2 == 0) ? ns / 2 : ns;
+    std::vector<int> rad;
+    if (!factor_radices(L, rad)) L = smooth_len_235(2L * L - 1);
+    const size_t tile_bytes = ((size_t)L + kTwLo + (size_t)(L + kTwLo - 1) / kTwLo) * sizeof(float2);
+    if (tile_bytes > kSpLdsMax) return 0;
+    int off = 0;
+    return noise_lds(ns, tile_bytes, L, &off) <= kSpLdsMax ? 1 : 0;
+}
+
+constexpr int kNoiseSlab = 65535;      // rows per pass of the long-row form (d4w_analytic_long_f32's grid limit)
+
+size_t d4w_channel_noise_ws_bytes(int nx, int ns) {
+    if (nx < 1 || ns < 2) return 0;
+    const int nb = std::min(nx, kNoiseSlab);
+    // the envelope, the gathered rows of a column window, the long transform's own scratch
+    return 2 * (size_t)nb * ns * sizeof(float) + d4w_analytic_long_ws_bytes(nb, ns);
+}
+
+int d4w_channel_noise_f32(const float* x, int nx, int ns, size_t ld, const double* q_host, int nq, float* mean_sq, float* sd,
+                          float* env_mean, float* env_q, void* ws, int how, void* stream) {
+    if (!x || nx < 1 || ns < 2 || ld < (size_t)ns) return fail(D4W_EINVAL, "bad argument");
+    if (how < 0 || how > 2) return fail(D4W_EINVAL, "how = %d not in 0..2", how);
+    SelRanks R;
+    int rc = sel_ranks(q_host, nq, (size_t)ns, &R);
+    if (rc) return rc;
+    if (nq == 0) env_q = nullptr;
+    if (!env_q) R.nq = 0;                                            // NULL like every other output: not formed
+    const bool fits = d4w_channel_noise_fits_lds(ns) != 0;
+    if (how == 1 && !fits) return fail(D4W_EINVAL, "rows of %d samples do not fit the one-read form (d4w_channel_noise_fits_lds)", ns);
+    if (how == 0) how = fits ? 1 : 2;
+    if (!mean_sq && !sd && !env_mean && !env_q) return D4W_OK;
+    if (how == 1) {
+        const bool packed = (ns % 2 == 0);
+        const int L = packed ? ns / 2 : ns;
+        const RowFftHost* h = nullptr;
+        rc = row_fft_get(L, &h);
+        if (rc) return rc;
+        int sel_off = 0;
+        const size_t lds = noise_lds(ns, row_tile_lds(h->dev), h->dev.bs_L ? h->dev.bs_L : L, &sel_off);
+        if (lds > kSpLdsMax) return fail(D4W_EINVAL, "rows of %d samples do not fit the one-read form", ns);
+        // 8-byte row loads only where every row starts on 8 bytes: decided from the pointer and the pitch, not from ns
+        const int al8 = ((reinterpret_cast<uintptr_t>(x) & 7) == 0 && (ld & 1) == 0) ? 1 : 0;
+        const int threads = L >= 2048 ? kAnMaxThreads : kSpThreads;
+#define D4W_NOISE(P, G)                                                                                  \
+    do {                                                                                                 \
+        sp_allow_lds(noise_rows<P, G>, lds);                                                             \
+        D4W_LAUNCH((noise_rows<P, G>), dim3(nx), dim3(threads), lds, stream, h->dev, x, ns, ld, al8,     \
+                   sel_off, R, mean_sq, sd, env_mean, env_q);                                            \
+    } while (0)
+        if (packed) { if (h->generic) D4W_NOISE(true, true); else D4W_NOISE(true, false); }
+        else { if (h->generic) D4W_NOISE(false, true); else D4W_NOISE(false, false); }
+#undef D4W_NOISE
+        return D4W_OK;
+    }
+    const bool want_env = env_mean || env_q;
+    if (want_env && !ws) return fail(D4W_EINVAL, "the long-row form needs the workspace of d4w_channel_noise_ws_bytes");
+    for (int a = 0; a < nx; a += kNoiseSlab) {
+        const int nb = std::min(nx - a, kNoiseSlab);
+        const float* xb = x + (size_t)a * ld;
+        if (mean_sq || sd)
+            D4W_LAUNCH(row_moments, dim3(nb), dim3(kSpThreads), 0, stream, xb, ns, ld, mean_sq ? mean_sq + a : nullptr,
+                       sd ? sd + a : nullptr);
+        if (!want_env) continue;
+        const int nws = std::min(nx, kNoiseSlab);
+        float* env = (float*)ws;
+        float* rows = env + (size_t)nws * ns;
+        void* lws = rows + (size_t)nws * ns;
+        if (ld != (size_t)ns) {
+            D4W_LAUNCH(gather_rows, dim3(std::min(ceil_div(ns, kSpThreads), 64), nb), dim3(kSpThreads), 0, stream, xb, ns, ld, rows);
+            xb = rows;
+        }
+        rc = d4w_analytic_long_f32(xb, env, nb, ns, kAnEnvelope, nullptr, 0.0, lws, stream);
+        if (rc) return rc;
+        D4W_LAUNCH(row_quantile, dim3(nb), dim3(kSpThreads), 0, stream, (const float*)env, (size_t)ns, (size_t)ns, R,
+                   env_q ? env_q + (size_t)a * R.nq : nullptr, env_mean ? env_mean + a : nullptr);
+    }
+    return D4W_OK;
+}
+
 int d4w_spectrocorr_f32(const float* S, int nx, int nf, int nt, const float* K, int nk, int off, int nout,
                         const float* med, int zero_ends, float* out, void* stream) {
     if (!S || !K || !med || !out || nx < 1 || nf < 1 || nt < 1 || nk < 1 || nout < 1)
@@ -1934,7 +2265,7 @@ int d4w_spectrocorr_f32(const float* S, int nx, int nf, int nt, const float* K, 
     return D4W_OK;
 }
 
-static int find_peaks_launch(const float* x, int nx, int ns, double prominence, const float* thr_dev, int32_t* idx,
+static int find_peaks_launch(const float* x, int nx, int ns, double prominence, const float* thr_dev, int thr_rows, int32_t* idx,
                              int32_t* counts, int cap, void* stream) {
     if (!x || !idx || !counts || nx < 1 || ns < 1 || cap < 1) return fail(D4W_EINVAL, "bad argument");
     int bshift = 5;                                            // 32-sample blocks, larger for very long rows
@@ -1949,24 +2280,30 @@ static int find_peaks_launch(const float* x, int nx, int ns, double prominence, 
     if (staged) {
         sp_allow_lds(find_peaks_prom<true>, lds);
         D4W_LAUNCH(find_peaks_prom<true>, dim3(nx), dim3(kFpThreads), lds, stream, x, ns, prominence, bshift, (int*)idx,
-                   (int*)counts, cap, thr_dev);
+                   (int*)counts, cap, thr_dev, thr_rows);
     } else {
         sp_allow_lds(find_peaks_prom<false>, lds);
         D4W_LAUNCH(find_peaks_prom<false>, dim3(nx), dim3(kFpThreads), lds, stream, x, ns, prominence, bshift, (int*)idx,
-                   (int*)counts, cap, thr_dev);
+                   (int*)counts, cap, thr_dev, thr_rows);
     }
     return D4W_OK;
 }
 
 int d4w_find_peaks_f32(const float* x, int nx, int ns, double prominence, int32_t* idx, int32_t* counts, int cap,
                        void* stream) {
-    return find_peaks_launch(x, nx, ns, prominence, nullptr, idx, counts, cap, stream);
+    return find_peaks_launch(x, nx, ns, prominence, nullptr, 0, idx, counts, cap, stream);
 }
 
 int d4w_find_peaks_dthr_f32(const float* x, int nx, int ns, const float* value, double scale, int32_t* idx, int32_t* counts,
                             int cap, void* stream) {
     if (!value) return fail(D4W_EINVAL, "NULL argument");
-    return find_peaks_launch(x, nx, ns, scale, value, idx, counts, cap, stream);
+    return find_peaks_launch(x, nx, ns, scale, value, 0, idx, counts, cap, stream);
+}
+
+int d4w_find_peaks_rowthr_f32(const float* x, int nx, int ns, const float* thr, double scale, int32_t* idx, int32_t* counts,
+                              int cap, void* stream) {
+    if (!thr) return fail(D4W_EINVAL, "NULL argument");
+    return find_peaks_launch(x, nx, ns, scale, thr, 1, idx, counts, cap, stream);
 }
 
 #ifdef D4W_FP_TIMING

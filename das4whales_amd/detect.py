@@ -293,6 +293,43 @@ class Threshold:
         return self.scale * float(self.value.cpu().reshape(-1)[0])
 
 
+class ChannelThreshold:
+    """One pick threshold per channel, formed on the device: scale x values[c] (values: a float32 CUDA [nx] tensor) -- "k times
+    this channel's noise floor", e.g. ChannelThreshold(8.0, dsp.channel_noise(x).env_quantiles[:, 0]) with the per-channel
+    median envelope of scripts/main_bathynoise.py:139,183.  No host wait; the product is formed in float64 like Threshold's.
+    As in SciPy a NaN or +inf bar yields no pick in its row, a zero or negative bar every strict local maximum.  Accepted
+    wherever pick_times / pick_times_env take a threshold."""
+
+    def __init__(self, scale, values):
+        if not (dev.is_tensor(values) and values.is_cuda and values.dtype == torch.float32 and values.dim() == 1 and values.numel() >= 1):
+            raise ValueError("values must be a float32 CUDA tensor with one value per channel")
+        self.scale, self.values = float(scale), values.contiguous()
+
+
+def _per_channel(threshold, nx):
+    """Host-side reading of a picker's threshold: None for the one-bar forms (a number, a Threshold), else the per-channel bars
+    as a ChannelThreshold or a float32 ndarray of nx values.  A wrong count raises ValueError -- before any device work."""
+    if isinstance(threshold, Threshold):
+        return None
+    if isinstance(threshold, ChannelThreshold):
+        n, bars = int(threshold.values.numel()), threshold
+    elif dev.is_tensor(threshold):
+        if threshold.dim() == 0 or (threshold.numel() == 1 and nx != 1):
+            return None                                              # float(threshold), as ever
+        if not (threshold.is_cuda and threshold.dtype == torch.float32):
+            raise ValueError("a per-channel threshold tensor must be a float32 CUDA tensor (or pass a NumPy array / list)")
+        n, bars = (int(threshold.numel()) if threshold.dim() == 1 else -1), ChannelThreshold(1.0, threshold.reshape(-1))
+    else:
+        if np.ndim(threshold) == 0 or (np.size(threshold) == 1 and nx != 1):
+            return None
+        bars = np.asarray(threshold, dtype=np.float32)
+        n = int(bars.size) if bars.ndim == 1 else -1
+    if n != nx:
+        raise ValueError("a per-channel threshold needs one value for each of the %d channels (got %s)"
+                         % (nx, "%d" % n if n >= 0 else "an array that is not 1-D"))
+    return bars
+
+
 def xcorr_continuation_ok(taps_list, ns, how=None):
     """Whether _xcorr_device(..., cont=...) applies: the matrix-core form, or two templates that run the fused overlap-save kernel.
     how: _xcorr_method(taps_list, ns, "auto") when the caller has resolved it already."""
@@ -758,7 +795,8 @@ _PICK_CAP_BYTES = 8 << 30            # ... while the index table stays below thi
 
 def _find_peaks_device(c, threshold, cap0=1024, lazy=False):
     """c: float32 CUDA [nx, ns] -> PickRows.  One host synchronisation per call (total and largest per-row count);
-    the ragged result is compacted on the device.  threshold: a number or a Threshold (formed on the device).  lazy=True:
+    the ragged result is compacted on the device.  threshold: a number, a Threshold (formed on the device), or one bar per
+    channel (a ChannelThreshold, or nx values as a NumPy array, list or float32 CUDA tensor).  lazy=True:
     the picker is launched and the synchronisation (and the compaction behind it) is left to the first look at the result
     -- a chain over many blocks keeps the device busy and looks at the end; `c` stays alive until then."""
     nx, ns = c.shape
@@ -771,6 +809,11 @@ def _find_peaks_device(c, threshold, cap0=1024, lazy=False):
     on_dev = isinstance(threshold, Threshold)
     if on_dev and threshold.value.device != c.device:
         raise ValueError("the threshold's value lives on another device than the block")
+    rows = _per_channel(threshold, nx)
+    if isinstance(rows, np.ndarray):
+        rows = ChannelThreshold(1.0, torch.from_numpy(rows).to(c.device))
+    if rows is not None and rows.values.device != c.device:
+        raise ValueError("the threshold's values live on another device than the block")
     cnt = torch.empty(nx, dtype=torch.int32, device=c.device)
     off = torch.empty(nx, dtype=torch.int64, device=c.device)
     summ = torch.empty(2, dtype=torch.int64, device=c.device)
@@ -778,7 +821,10 @@ def _find_peaks_device(c, threshold, cap0=1024, lazy=False):
 
     def launch(cap):
         idx = torch.empty((nx, cap), dtype=torch.int32, device=c.device)
-        if on_dev:
+        if rows is not None:
+            check(lib.d4w_find_peaks_rowthr_f32(dev.ptr(c), nx, ns, dev.ptr(rows.values), rows.scale, dev.ptr(idx),
+                                                dev.ptr(cnt), cap, int(stream.cuda_stream)))
+        elif on_dev:
             check(lib.d4w_find_peaks_dthr_f32(dev.ptr(c), nx, ns, dev.ptr(threshold.value), threshold.scale, dev.ptr(idx),
                                               dev.ptr(cnt), cap, int(stream.cuda_stream)))
         else:
@@ -809,11 +855,13 @@ def _find_peaks_device(c, threshold, cap0=1024, lazy=False):
 
 
 def pick_times_env(corr_m, threshold, lazy=False):
-    """Per row find_peaks(|hilbert(corr)|, prominence=threshold)[0] -- reference detect.py:169-195.  threshold: a number or a
-    Threshold (formed on the device); lazy: see _find_peaks_device (both beyond the reference's signature)."""
+    """Per row find_peaks(|hilbert(corr)|, prominence=threshold)[0] -- reference detect.py:169-195.  threshold: a number, a
+    Threshold (formed on the device) or one bar per channel (a ChannelThreshold, or nx values as a NumPy array, list or float32
+    CUDA tensor: row c is picked with prominence=threshold[c]); lazy: see _find_peaks_device (both beyond the reference's signature)."""
     from . import dsp
     if getattr(corr_m, "ndim", 0) != 2:
         raise ValueError("corr_m must be a 2-D [channel x time] array")
+    _per_channel(threshold, int(corr_m.shape[0]))
     env = dsp._analytic(dev.to_device_f32(corr_m), 0)
     return _find_peaks_device(env, threshold, lazy=lazy)
 
@@ -834,6 +882,7 @@ def pick_times(corr_m, threshold, lazy=False):
     """Per row find_peaks(corr, prominence=threshold)[0] -- reference detect.py:249-274 (threshold / lazy: pick_times_env)."""
     if getattr(corr_m, "ndim", 0) != 2:
         raise ValueError("corr_m must be a 2-D [channel x time] array")
+    _per_channel(threshold, int(corr_m.shape[0]))
     return _find_peaks_device(dev.to_device_f32(corr_m), threshold, lazy=lazy)
 
 

@@ -5,7 +5,9 @@ arithmetic runs in the HIP library (include/d4w.h).  Filter *design* of 1-D IIR 
 on the host in float64 (SciPy), exactly like the reference does.
 """
 import atexit
+import collections
 import ctypes
+import operator
 import threading
 import weakref
 
@@ -1091,6 +1093,116 @@ def get_fx(trace, nfft):
     with torch.cuda.device(x.device):
         check(lib.d4w_fx_f32(dev.ptr(x), dev.ptr(y), nx, ns, int(nfft), dev.stream_ptr(x)))
     return dev.like_input(y, trace)
+
+
+# ---------------------------------------------------------------------------------------------
+# noise along the cable (reference scripts/main_bathynoise.py: no function there, the numbers are formed inline)
+# ---------------------------------------------------------------------------------------------
+ChannelNoise = collections.namedtuple("ChannelNoise", ["mean_square", "std", "env_mean", "env_quantiles"])
+_NOISE_HOW = {"auto": 0, "one_read": 1, "long_row": 2}
+
+
+def row_quantile_limit():
+    """The largest number of quantiles one call takes."""
+    m = ctypes.c_int()
+    check(lib.d4w_row_quantile_limits(ctypes.byref(m)))
+    return m.value
+
+
+def _quantile_list(q):
+    """(float64 values, scalar?) -- checked on the host: inside [0, 1], no more than the limit."""
+    scalar = np.ndim(q) == 0
+    qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if qs.ndim != 1:
+        raise ValueError("quantiles must be a number or a 1-D sequence of numbers")
+    if not np.all((qs >= 0.0) & (qs <= 1.0)):
+        raise ValueError("quantiles must lie in [0, 1]")
+    if qs.size > row_quantile_limit():
+        raise ValueError("at most %d quantiles per call (got %d)" % (row_quantile_limit(), qs.size))
+    return qs, scalar
+
+
+def row_quantile(x, q):
+    """np.quantile(x, q, axis=-1) of every row with NumPy's default "linear" method, from exact order statistics (a radix
+    select, include/d4w.h d4w_row_quantile_f32): [nx, nq], or [nx] for a scalar q; a 1-D x is one row.  A row that holds a
+    NaN gives NaN.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensor out."""
+    qs, scalar = _quantile_list(q)
+    if qs.size == 0:
+        raise ValueError("no quantile given")
+    x2, was1d = _rows_2d(x)
+    if x2.shape[0] < 1 or x2.shape[1] < 1:
+        raise ValueError("x must not be empty")
+    xd = dev.to_device_f32(x2)
+    nx, n = xd.shape
+    out = torch.empty((nx, qs.size), dtype=torch.float32, device=xd.device)
+    with torch.cuda.device(xd.device):
+        check(lib.d4w_row_quantile_f32(dev.ptr(xd), nx, n, n, qs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(qs.size),
+                                       dev.ptr(out), dev.stream_ptr(xd)))
+    out = out[:, 0] if scalar else out
+    return dev.like_input(out[0] if was1d else out, x)
+
+
+def channel_noise(trace, quantiles=(0.5,), window=None, *, how="auto"):
+    """The noise floor of every channel in one read of the block -- scripts/main_bathynoise.py:139,183-194 (median and mean of
+    the envelope, standard deviation per channel) and :256-259 (mean square and mean envelope of a quiet window).  Returns
+    ChannelNoise(mean_square [nx], std [nx], env_mean [nx], env_quantiles [nx, nq]), float32:
+        mean(x^2), np.std(x), mean(|hilbert(x)|), np.quantile(|hilbert(x)|, quantiles) of every row x.
+    window=(a, b) in samples is the reference's trf_fk[:, a:b], read in place (no copy); the Hilbert transform is that of the
+    window.  how: "auto", "one_read" (rows that fit one workgroup's LDS: nothing of the block's size is written) or "long_row"
+    (envelope through HBM); include/d4w.h d4w_channel_noise_f32.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out."""
+    if getattr(trace, "ndim", 0) != 2 or trace.shape[0] < 1 or trace.shape[1] < 1:
+        raise ValueError("trace must be a non-empty 2-D [channel x time] array")
+    qs, _ = _quantile_list(quantiles)
+    if how not in _NOISE_HOW:
+        raise ValueError("how must be one of %s" % sorted(_NOISE_HOW))
+    nx, ns0 = int(trace.shape[0]), int(trace.shape[1])
+    a, b = 0, ns0
+    if window is not None:
+        try:
+            a, b = (operator.index(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError("window must be a pair of sample indices (a, b)") from None
+        if not 0 <= a < b <= ns0:
+            raise ValueError("window (%d, %d) must satisfy 0 <= a < b <= %d" % (a, b, ns0))
+    ns = b - a
+    if ns < 2:
+        raise ValueError("a row of %d sample has no Hilbert transform" % ns)
+    code = _NOISE_HOW[how]
+    if code == 1 and not lib.d4w_channel_noise_fits_lds(ns):
+        raise ValueError("rows of %d samples do not fit the one-read form" % ns)
+    x = dev.to_device_f32(trace)
+    nq = int(qs.size)
+    out = torch.empty((3, nx), dtype=torch.float32, device=x.device)
+    eq = torch.empty((nx, nq), dtype=torch.float32, device=x.device)
+    long_row = code == 2 or (code == 0 and not lib.d4w_channel_noise_fits_lds(ns))
+    with torch.cuda.device(x.device):
+        ws = None
+        if long_row:
+            if nx <= 65535:
+                _auto_specialise(nx, ns)
+            ws = torch.empty(int(lib.d4w_channel_noise_ws_bytes(nx, ns)), dtype=torch.uint8, device=x.device)
+        check(lib.d4w_channel_noise_f32(dev.ptr(x) + 4 * a, nx, ns, ns0, qs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), nq,
+                                        dev.ptr(out[0]), dev.ptr(out[1]), dev.ptr(out[2]), dev.ptr(eq) if nq else None,
+                                        dev.ptr(ws) if ws is not None else None, code, dev.stream_ptr(x)))
+    if dev.is_tensor(trace):
+        back = (lambda t: t) if trace.is_cuda else (lambda t: t.to(trace.device))
+    else:
+        back = lambda t: t.cpu().numpy()
+    return ChannelNoise(back(out[0]), back(out[1]), back(out[2]), back(eq))
+
+
+def noise_ratio_db(std, env_median):
+    """20 log10(std / env_median) -- scripts/main_bathynoise.py:194, float64.  IEEE results without warnings (0 / 0 and every
+    NaN give NaN, a zero median +inf).  Small arithmetic on the container it was given: NumPy in -> NumPy out, a tensor in ->
+    a tensor on its device."""
+    d = next((v.device for v in (std, env_median) if dev.is_tensor(v) and v.is_cuda), None)
+    if d is not None:
+        s, m = ((v if dev.is_tensor(v) else torch.from_numpy(np.asarray(v))).to(d, torch.float64) for v in (std, env_median))
+        return 20.0 * torch.log10(s / m)
+    s, m = (np.asarray(v.numpy() if dev.is_tensor(v) else v, dtype=np.float64) for v in (std, env_median))
+    with np.errstate(all="ignore"):
+        r = np.asarray(20.0 * np.log10(s / m))
+    return torch.from_numpy(r) if dev.is_tensor(std) or dev.is_tensor(env_median) else r
 
 
 def _welch(x2d, fs, nperseg, noverlap, chunk):

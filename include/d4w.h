@@ -625,6 +625,40 @@ int d4w_spectrocorr_f32(const float* S, int nx, int nf, int nt, const float* K, 
                         int nout, const float* med, int zero_ends, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exact order statistics of every row: out[c][j] = np.quantile(v[c][0:per_row].astype(float64), q[j]) with NumPy's default
+ * "linear" method, rounded once to float32 -- the per-channel median of scripts/main_bathynoise.py:139 and any other quantile
+ * of a row.  With h = q (n - 1): the order statistics of ranks floor(h) and floor(h) + 1 (the last one twice at q = 1), exact,
+ * by a radix select on order-preserving keys (no sort, no sample), interpolated in float64 by NumPy's own formula -- so a row
+ * with infinities gives what NumPy gives, a NaN where NumPy's a + (b - a) g meets inf - inf or inf * 0.
+ *   v: DEVICE, rows `ld` elements apart (a column window of a block is read in place); q_host: HOST [nq], 0 <= q <= 1;
+ *   nq in 1 .. d4w_row_quantile_limits (8).  A row that holds a NaN gives NaN for every q; -0 and +0 are equal.
+ * All nq quantiles come out of one launch: one sweep of the row shared by all of them, two more per quantile.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_row_quantile_f32(const float* v, int nx, size_t per_row, size_t ld, const double* q_host, int nq,
+                         float* out, void* stream);
+int d4w_row_quantile_limits(int* max_q);
+
+/* ------------------------------------------------------------------------------------------
+ * The noise floor of every channel (scripts/main_bathynoise.py): per row c of x [nx][ns] (rows `ld` elements apart: a time
+ * window of a block is read in place, and the Hilbert transform is that of the window, main_bathynoise.py:256-259)
+ *   mean_sq[c]  = np.mean(x**2)                               main_bathynoise.py:257
+ *   std[c]      = np.std(x)  (population)                     main_bathynoise.py:189
+ *   env_mean[c] = np.mean(abs(scipy.signal.hilbert(x)))       main_bathynoise.py:186,259
+ *   env_q[c][j] = np.quantile(abs(hilbert(x)), q[j])          main_bathynoise.py:139,183 (q = 0.5), d4w_row_quantile_f32's definition
+ * The envelope is d4w_analytic_f32's mode 0.  Every output pointer may be NULL; nq = 0 .. 8 (env_q NULL with nq = 0); sums in
+ * float64 in an order that depends on ns and the form alone (bit-identical run to run, whatever nx and the other rows).
+ *   how = 1  one-read form, rows with d4w_channel_noise_fits_lds(ns) = 1: one workgroup per row transforms it in LDS, keeps
+ *            the envelope there and selects from LDS -- one read of the block, nx (3 + nq) floats written; ws is not used.
+ *   how = 2  long-row form, any ns: envelope by d4w_analytic_long_f32 into ws (DEVICE, d4w_channel_noise_ws_bytes(nx, ns)),
+ *            then the select and a moment sweep over global memory; nx > 65535 in slabs.
+ *   how = 0  the one-read form where it fits, else the long-row form.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_channel_noise_fits_lds(int ns);
+size_t d4w_channel_noise_ws_bytes(int nx, int ns);
+int d4w_channel_noise_f32(const float* x, int nx, int ns, size_t ld, const double* q_host, int nq,
+                          float* mean_sq, float* std, float* env_mean, float* env_q, void* ws, int how, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Peak picking: scipy.signal.find_peaks(x[c], prominence=thr)[0] per row, replaces the loops of
  * detect.pick_times / pick_times_env / process_corr / pick_times_par (detect.py:169-274; the
  * envelope of the *_env variants is d4w_analytic_f32 mode 0).  Strict local maxima with plateaus
@@ -640,6 +674,11 @@ int d4w_find_peaks_f32(const float* x, int nx, int ns, double prominence, int32_
  * threshold from the block's largest correlation (d4w_minmax_f32, d4w_xcorr_mm_rowmax_f32) need not wait for it. */
 int d4w_find_peaks_dthr_f32(const float* x, int nx, int ns, const float* value, double scale, int32_t* idx,
                             int32_t* counts, int cap, void* stream);
+/* One threshold per row: prominence of row c = scale * (double)thr[c], thr DEVICE [nx] -- "k times this channel's noise floor"
+ * (the per-channel median envelope of scripts/main_bathynoise.py:139,183 from d4w_channel_noise_f32).  As in SciPy a NaN or
+ * +inf bar yields no pick in its row and a zero or negative bar every strict local maximum. */
+int d4w_find_peaks_rowthr_f32(const float* x, int nx, int ns, const float* thr, double scale, int32_t* idx,
+                              int32_t* counts, int cap, void* stream);
 /* offsets[c] = counts[0] + ... + counts[c] (int64, what d4w_pack_picks_i64 places the rows by) and
  * summary2 = {max_c counts[c], sum_c counts[c]} (DEVICE int64[2]: the capacity check and the table size of one picker call). */
 int d4w_pick_offsets_i64(const int32_t* counts, int nx, int64_t* offsets, int64_t* summary2, void* stream);
