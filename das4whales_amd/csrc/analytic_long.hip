@@ -2,7 +2,7 @@
  * Analytic signal of rows too long for one workgroup's LDS (e.g. 120 000 samples): the four-step
  * time phase of the distributed plan over ALL rows (world = 1), the Hilbert pair op on the packed
  * spectrum, the inverse time phase, and one elementwise combine with x.  Same modes as
- * d4w_analytic_f32 (spectral.hip).  ws: [nx][ns] float32 scratch.
+ * d4w_analytic_f32 (analytic.hip).  ws: [nx][ns] float32 scratch.
  * ------------------------------------------------------------------------------------------ */
 #include <cmath>
 #include <map>

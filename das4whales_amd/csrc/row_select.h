@@ -1,4 +1,4 @@
-// Exact order statistics of one row by a radix select on order-preserving keys (the keys of med_key in spectral.hip: sign
+// Exact order statistics of one row by a radix select on order-preserving keys (the keys of med_key in noise.hip: sign
 // flipped, negative values complemented), written once for a row in global memory (d4w_row_quantile_f32, the long-row form of
 // d4w_channel_noise_f32) and for a row that sits in LDS (the one-read form of d4w_channel_noise_f32): the row is a plain
 // `const float*` either way and every function is inlined into its kernel, so the compiler sees which address space it is.

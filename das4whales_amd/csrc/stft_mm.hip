@@ -3,7 +3,7 @@
 // periodic Hann, center = True with zero padding, bins 14-30 Hz kept).
 //
 // With 95 % overlap a frame-by-frame FFT transforms every sample twenty times: the register-FFT kernel of rounds 2-3
-// (spectral.hip: stft_fat) spends ~35 Gflop per 11 020 x 12 000 file and is bound by VALU issue (1.5 ms).  Only the 13 bins
+// (stft.hip: stft_fat) spends ~35 Gflop per 11 020 x 12 000 file and is bound by VALU issue (1.5 ms).  Only the 13 bins
 // between 14 and 30 Hz are kept, and then the transform is a small dense product with a Hankel factor,
 //
 //      X[b][t] = sum_u  w[u] e^{-2 pi i b u / N} * x[hop t - N/2 + u],      b in the kept bins,  u < N,

@@ -9,10 +9,9 @@
 // are not read twice), two real segments ride one complex transform z = s_a + i s_b of fft_lds.h,
 // and |Z|^2 is summed per LDS position in float64: no untangling is needed for the average, since
 // |S_a[k]|^2 + |S_b[k]|^2 = (|Z[k]|^2 + |Z[N-k]|^2) / 2.  k is folded with N - k once per chunk.
-#include <map>
-#include <mutex>
-
-#include "fft_host.h"
+// The segment transform's tables (stage radices, positions, periodic Hann and its float64 sum of squares) are the row
+// operators' plan of the same length (row_fft.h).
+#include "row_fft.h"
 
 namespace d4w {
 
@@ -20,70 +19,6 @@ constexpr int kWelchThreads = 256;
 constexpr int kWelchMinSeg = 16, kWelchMaxSeg = 4096;
 constexpr int kWelchTile = 4096;                               // complex LDS elements of a group of segment pairs
 constexpr int kWelchMaxPairs = 16;
-
-// per-(device, nperseg) tables, cached for the life of the process
-struct WelchDev {
-    AxisDesc ax;
-    const int* pos;       // [N] frequency -> LDS position after the forward (DIF) transform
-    const float* hann;    // [N] scipy.signal.get_window('hann', N): periodic
-};
-struct WelchHost {
-    WelchDev dev;
-    bool generic;
-    double sumw2;         // sum(w^2) of the float64 window, SciPy's density scale
-};
-
-static std::mutex g_welch_mu;
-static std::map<std::pair<int, int>, WelchHost*> g_welch;
-
-template <typename T>
-static int welch_upload(std::vector<void*>& allocs, const std::vector<T>& v, const T** out) {
-    void* p = nullptr;
-    D4W_HIP(hipMalloc(&p, v.size() * sizeof(T)));
-    allocs.push_back(p);
-    D4W_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = (const T*)p;
-    return D4W_OK;
-}
-
-static int welch_get(int N, const WelchHost** out) {
-    int devid = 0;
-    D4W_HIP(hipGetDevice(&devid));
-    std::lock_guard<std::mutex> lk(g_welch_mu);
-    auto it = g_welch.find({devid, N});
-    if (it != g_welch.end()) { *out = it->second; return D4W_OK; }
-    std::vector<int> rad;
-    if (!factor_radices(N, rad)) return fail(D4W_EINVAL, "nperseg = %d has a prime factor > 31", N);
-    WelchHost* h = new WelchHost();
-    memset(&h->dev, 0, sizeof(h->dev));
-    AxisDesc& ax = h->dev.ax;
-    ax.L = N;
-    ax.nstage = (int)rad.size();
-    for (int i = 0; i < kMaxStages; ++i) ax.radix[i] = (i < (int)rad.size()) ? rad[i] : 1;
-    const std::vector<int> p2f = pos_to_freq(N, rad);
-    std::vector<int> pos(N);
-    for (int p = 0; p < N; ++p) pos[p2f[p]] = p;
-    std::vector<float> hann(N);
-    h->sumw2 = 0.0;
-    for (int n = 0; n < N; ++n) {
-        const double w = 0.5 - 0.5 * cos(2.0 * M_PI * (double)n / (double)N);
-        hann[n] = (float)w;
-        h->sumw2 += w * w;
-    }
-    std::vector<void*> allocs;
-    int rc = welch_upload(allocs, twiddle_table2(N, &ax.nhi), &ax.tw2);
-    if (!rc) rc = welch_upload(allocs, pos, &h->dev.pos);
-    if (!rc) rc = welch_upload(allocs, hann, &h->dev.hann);
-    if (rc) {
-        for (void* p : allocs) (void)hipFree(p);
-        delete h;
-        return rc;
-    }
-    h->generic = axis_needs_generic(ax);
-    g_welch[{devid, N}] = h;
-    *out = h;
-    return D4W_OK;
-}
 
 struct WelchDims {
     int ns, chunk, nchunks;
@@ -121,7 +56,7 @@ __device__ __forceinline__ void welch_stage(const float* __restrict__ src, float
 }
 
 template <bool GENERIC>
-__global__ __launch_bounds__(kWelchThreads) void welch_chunks(WelchDev F, WelchDims d, const float* __restrict__ x,
+__global__ __launch_bounds__(kWelchThreads) void welch_chunks(RowFftDev F, WelchDims d, const float* __restrict__ x,
                                                               float* __restrict__ pxx) {
     D4W_DYN_LDS(smem_raw);
     const int tid = threadIdx.x, N = d.N;
@@ -262,8 +197,8 @@ int d4w_welch_f32(const float* x, int nx, int ns, int chunk, int nperseg, int no
     if (!(fs > 0.0)) return fail(D4W_EINVAL, "fs = %g must be positive", fs);
     const int nchunks = ns / chunk;
     if ((long long)nx * nchunks > 0x7FFFFFFFLL) return fail(D4W_EINVAL, "nx x chunks = %d x %d exceeds the grid limit", nx, nchunks);
-    const WelchHost* h = nullptr;
-    int rc = welch_get(nperseg, &h);
+    const RowFftHost* h = nullptr;
+    int rc = row_fft_get(nperseg, &h);      // (never a Bluestein plan: d4w_welch_supported above)
     if (rc) return rc;
     WelchDims d;
     d.ns = ns; d.chunk = chunk; d.nchunks = nchunks;
@@ -275,14 +210,12 @@ int d4w_welch_f32(const float* x, int nx, int ns, int chunk, int nperseg, int no
     const size_t lds = (size_t)d.nb * nperseg * sizeof(float2) + (size_t)nperseg * sizeof(double) + (size_t)d.seg_cap * sizeof(float) + (size_t)nperseg * sizeof(float)
                        + (size_t)2 * d.nb * sizeof(Mean2) + (size_t)(kTwLo + h->dev.ax.nhi) * sizeof(float2);
     const dim3 grid((unsigned)((long long)nx * nchunks));
-    if (h->generic) {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)welch_chunks<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        D4W_LAUNCH(welch_chunks<true>, grid, dim3(kWelchThreads), lds, stream, h->dev, d, x, pxx);
-    } else {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)welch_chunks<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        D4W_LAUNCH(welch_chunks<false>, grid, dim3(kWelchThreads), lds, stream, h->dev, d, x, pxx);
-    }
-    return D4W_OK;
+    return with_flag(h->generic, [&](auto G) {
+        constexpr auto kern = welch_chunks<decltype(G)::value>;
+        allow_lds(kern, lds);
+        D4W_LAUNCH(kern, grid, dim3(kWelchThreads), lds, stream, h->dev, d, x, pxx);
+        return (int)D4W_OK;
+    });
 }
 
 int d4w_chunk_energy_f32(const float* x, int nx, int ns, int chunk, float* e, void* stream) {

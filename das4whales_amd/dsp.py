@@ -1021,7 +1021,7 @@ def fk_filt(data, tint, fs, xint, dx, c_min, c_max):
 
 
 # ---------------------------------------------------------------------------------------------
-# spectral views / metrics (row operators of csrc/spectral.hip)
+# spectral views / metrics (row operators of csrc/analytic.hip, stft.hip, noise.hip, spectrocorr.hip, peaks.hip)
 # ---------------------------------------------------------------------------------------------
 def _analytic(x2d, mode, fs=0.0, var=None):
     """x2d: float32 CUDA [nx, ns]; mode as in include/d4w.h d4w_analytic_f32."""

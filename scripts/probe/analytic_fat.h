@@ -7,7 +7,7 @@
 // twiddle powers cost about as many instructions per row (~28 K wave-instructions against 24 K) -- 6000 = 2^4 3 5^3 has no cheap
 // large radix -- and the 56-KB tile + 161 VGPRs leave two workgroups of 7 waves per compute unit instead of three of 8.
 // The host side (tables: W_N2^j, W_M1^(j2 b), the untangle twiddle of a group's first frequency, the mirror group) is in git
-// history of round 5 (commit "analytic_fat"); to try again paste this before row_var in csrc/spectral.hip.
+// history of round 5 (commit "analytic_fat"); to try again paste this before row_var in csrc/analytic.hip.
 // ---------------------------------------------------------------------------------------------
 // The same operator for the row lengths that matter (the 60-s file at 200 Hz: 12 000 samples) as THREE register-resident
 // radix stages with compile-time indices -- the structure of the f-k filter's pass B (fk_fast.h: fkf_passB with the Hilbert

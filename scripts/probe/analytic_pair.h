@@ -1,4 +1,4 @@
-// Experiment, not built (round 6): the analytic signal of a row (scipy.signal.hilbert; spectral.hip analytic_rows) with the
+// Experiment, not built (round 6): the analytic signal of a row (scipy.signal.hilbert; analytic.hip analytic_rows) with the
 // butterflies in PACKED registers -- the row's two half-length sub-transforms on the halves of 64-bit register pairs
 // (fft_pair.h), one 16-byte LDS word per index.  Correct (the emulator suite and 57 GPU tests green with it as the default,
 // 2e-7 .. 1e-6 against SciPy) and SLOWER: 0.65-0.66 ms per 11 020 x 12 000 block against 0.57-0.59 ms for analytic_rows on the
@@ -10,7 +10,7 @@
 // workgroups per compute unit instead of three) and five busy waves per stage more than give back.  The matrix cores do not
 // help either: a radix-r stage as a split-binary16 product is 3 x 8 r flop per point plus the same conversions and twiddle
 // multiplications on the vector unit that the butterfly costs today.
-// To try again: paste this before row_var in csrc/spectral.hip, #include "fft_pair.h", and launch it from d4w_analytic_f32
+// To try again: paste this before row_var in csrc/analytic.hip, #include "fft_pair.h", and launch it from d4w_analytic_f32
 // for ns % 4 == 0, ns / 4 = 2^a 3^b 5^c, modes 0, 1, 2, 4:
 //     if (mode != kAnIfreq && ns % 4 == 0 && ns >= 64 && h->dev.bs_L == 0 && !h->generic) {      // h = row_fft_get(ns / 2)
 //         const RowFftHost* hh = nullptr;  rc = row_fft_get(ns / 4, &hh);  if (rc) return rc;

@@ -6,7 +6,7 @@
 // row; fused, a workgroup holds the picker's tables AND the transform tile (75 KB: two per compute unit instead of three) and
 // runs the two chains one after the other, where the two launches overlap rows of different phases across workgroups.  The
 // 1 GB of envelope traffic it saves per correlogram is ~0.2 ms of HBM time -- less than the occupancy it costs.
-// To try it again: paste into csrc/spectral.hip before pack_picks, add the entry points (d4w_find_peaks_env_fits / _f32).
+// To try it again: paste into csrc/peaks.hip before pack_picks, add the entry points (d4w_find_peaks_env_fits / _f32).
 // detect.pick_times_env in ONE launch: find_peaks(|hilbert(row)|, prominence) with the envelope formed in the LDS row the
 // picker works on (analytic_rows' packed transform, in place: the pair (H[2m], H[2m+1]) becomes (|z[2m]|, |z[2m+1]|) at the
 // same 8 bytes) -- the envelope is never written to memory and never read back: 4 B read per sample instead of 4 + 4 + 4.

@@ -19,7 +19,7 @@
 // ---------------------------------------------------------------------------------------------
 // The spectrogram detector of one channel in ONE launch (round 6): detect.compute_cross_correlogram_spectrocorr
 // (reference detect.py:650-709) is, per channel, STFT magnitudes -> np.median of the kept bins -> kernel correlation along
-// time, clipped at zero, over (median x kernel length).  As three launches (stft_mm_rows, spectral.hip row_median,
+// time, clipped at zero, over (median x kernel length).  As three launches (stft_mm_rows, noise.hip row_median,
 // spectro_corr) the 13 x 1501 magnitudes of a 60-s channel were written once and read two to four times: 0.86 GB per
 // 11 020-channel file each way, 1.24 ms of the stream's 5 ms.  They are 78 KB per channel -- they fit the LDS of a compute
 // unit.  One 512-thread workgroup owns a compute unit and walks channels: the row's samples are staged as binary16 hi / lo
@@ -47,7 +47,7 @@ struct SfArgs {
     int dbg;
 };
 
-__device__ __forceinline__ unsigned sf_key(float v) {              // order-preserving keys (spectral.hip med_key)
+__device__ __forceinline__ unsigned sf_key(float v) {              // order-preserving keys (noise.hip med_key)
     const unsigned b = __float_as_uint(v);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }

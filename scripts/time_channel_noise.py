@@ -1,4 +1,4 @@
-"""Time dsp.channel_noise (csrc/spectral.hip noise_rows / row_quantile / row_moments) on a resident CUDA block: HIP events
+"""Time dsp.channel_noise (csrc/noise.hip noise_rows / row_quantile / row_moments) on a resident CUDA block: HIP events
 around each call, warm-ups first, median (and spread) of --reps calls, the variants alternated.
 
 Per shape (default 11020 x 12000, the one-read form; 20000x120000 is the long-row form):

@@ -1,5 +1,5 @@
 """Cases, inputs and float64 references of the spectrogram detector chain (STFT -> row median -> kernel x spectrogram
-correlation, csrc/spectral.hip and csrc/stft_mm.hip), shared by tests/test_emu_spectrocorr.py (CPU emulator, C ABI) and
+correlation, csrc/stft.hip, csrc/noise.hip, csrc/spectrocorr.hip and csrc/stft_mm.hip), shared by tests/test_emu_spectrocorr.py (CPU emulator, C ABI) and
 tests/test_spectrocorr_gpu.py (Python interface on the device).
 
 References are written as the reference package writes them, in float64 on inputs rounded to float32 first:

@@ -1,4 +1,4 @@
-"""Row quantiles, the per-channel noise floor and per-row pick thresholds (csrc/row_select.h, csrc/spectral.hip) in the CPU
+"""Row quantiles, the per-channel noise floor and per-row pick thresholds (csrc/row_select.h, csrc/noise.hip, csrc/peaks.hip) in the CPU
 emulator build through the C ABI on host pointers, against the float64 restatement of tests/known_answers_noise.py.  Kernel
 logic only; the cases and bars are those of tests/noise_cases.py, which the hardware runs as well (tests/test_noise_gpu.py).
 Every output lies between guards that must come back untouched.  No case is skipped or excluded."""

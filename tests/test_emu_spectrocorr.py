@@ -1,4 +1,4 @@
-"""The spectrogram detector chain (STFT, row median, kernel x spectrogram correlation: csrc/spectral.hip, csrc/stft_mm.hip)
+"""The spectrogram detector chain (STFT, row median, kernel x spectrogram correlation: csrc/stft.hip, csrc/noise.hip, csrc/spectrocorr.hip, csrc/stft_mm.hip)
 on the CPU emulator build: same HIP source, same C ABI, host pointers, against the float64 references of
 tests/spectro_cases.py (cases, tolerances and why the long kernels use integer inputs: there)."""
 import ctypes

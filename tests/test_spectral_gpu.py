@@ -170,7 +170,7 @@ def test_picks_random_rows_vs_scipy(dw):
 
 def test_picks_with_few_candidates_vs_scipy(dw):
     """The regime of the detection chain: smooth envelopes, the threshold a fraction of the strongest peak, ~10 maxima worth a
-    prominence walk per row (a group of lanes per walk side, hot blocks marked by half a wave each -- spectral.hip fp_scan);
+    prominence walk per row (a group of lanes per walk side, hot blocks marked by half a wave each -- peaks.hip fp_scan);
     bursts cut by the row ends, plateaus, rows of 12 000 (staged in LDS) and 20 000 samples (read in place), every row
     against SciPy at several thresholds; the same picks with the threshold formed on the device (detect.Threshold) and
     with the result looked at later (lazy=True)."""
@@ -205,7 +205,7 @@ def test_picks_with_few_candidates_vs_scipy(dw):
 
 def test_picks_long_rows_window_sweep_vs_scipy(dw):
     """Rows beyond the LDS staging limit (detect.pick_times on raw 120 000-sample correlograms, detect.py:249-274): the
-    windowed sweep over turning points (spectral.hip fp_sweep_segments) -- raw correlograms of noise (a maximum every ~9
+    windowed sweep over turning points (peaks.hip fp_sweep_segments) -- raw correlograms of noise (a maximum every ~9
     samples), their envelopes (a handful per window: the row falls back to the marking sweep), rows that change character
     half way, quantised rows (plateaus) -- every row against SciPy, with enough rows to have several workgroups per CU."""
     import scipy.signal as sps
