@@ -544,7 +544,7 @@ __device__ __forceinline__ void fp_scan(const float* __restrict__ r, const FpLds
                 if (m) {
                     const int cnt = __popc(m);
                     int p = atomicAdd(ccount, cnt);
-                    if (p + cnt + nhot <= kFpList) {
+                    if (p + cnt + nhot <= kFpList) {      // always: by_block has at most nb / 4 <= 128 hot blocks of at most 16 maxima each (no input reaches the else)
                         while (m) {
                             const int bit = __builtin_ctz(m);
                             m &= m - 1u;
@@ -642,8 +642,9 @@ __device__ __forceinline__ void fp_scan(const float* __restrict__ r, const FpLds
                 const double dl = (double)v - thr;
                 float lim = (float)dl;
                 if ((double)lim > dl) lim = nextafterf(lim, -INFINITY);
-                if (c2 & 1) ok = !(fp_walk<+1>(r, T.s1, T.s2, ns, nb, nb2, bshift, ia, v, lim) > lim);
-                else ok = !(fp_walk<-1>(r, T.s1, T.s2, ns, nb, nb2, bshift, i - 1, v, lim) > lim);    // left base too high
+                // (<= lim, not !(> lim): lim is NaN for a +inf sample under a +inf bar, and fp_walk_wave's ballots reject that side)
+                if (c2 & 1) ok = fp_walk<+1>(r, T.s1, T.s2, ns, nb, nb2, bshift, ia, v, lim) <= lim;
+                else ok = fp_walk<-1>(r, T.s1, T.s2, ns, nb, nb2, bshift, i - 1, v, lim) <= lim;    // else: left base too high
             }
             if (!ok) atomicOr(&cfail[c >> 5], 1u << (c & 31));
         }
@@ -779,7 +780,7 @@ __global__ __launch_bounds__(kFpThreads) void find_peaks_prom(const float* __res
     // host waiting for that maximum), formed in float64 like the host's 0.45 * float(c.max())
     // thr_rows: one value per row (d4w_find_peaks_rowthr_f32: "k times this channel's noise floor")
     const double thr = thr_dev ? thr0 * (double)thr_dev[thr_rows ? blockIdx.x : 0] : thr0;
-    if (thr_rows && !(thr == thr)) {                           // a NaN bar: no prominence is >= NaN (SciPy returns no peak)
+    if (!(thr == thr)) {                                       // a NaN bar, through any entry point: no prominence is >= NaN (SciPy returns no peak)
         if (threadIdx.x == 0) counts[blockIdx.x] = 0;
         return;
     }
@@ -818,7 +819,7 @@ __global__ __launch_bounds__(kFpThreads) void find_peaks_prom(const float* __res
         // A peak's prominence is its height less the higher of two minima of the row: never more than (row maximum - row minimum).
         // A row that cannot reach the threshold -- most channels of a file carry no call above 0.45 of the file's largest
         // correlation -- is done here: no candidates, no walks, no bitmap scan.  (Exact: the difference is formed in float64 like the walks', and the
-        // test is false for a NaN, which then takes the full path.)
+        // test is false for a row holding a NaN, which then takes the full path; a NaN bar has left above.)
         float gmax = -INFINITY, gmin2 = INFINITY;
         for (int k = 0; k < nb2; ++k) { const float2 e = T.s2[k]; gmax = fmaxf(gmax, e.x); gmin2 = fminf(gmin2, e.y); }
         if ((double)gmax - (double)gmin2 < thr) {

@@ -281,7 +281,10 @@ def correlogram_max(c, row_max=None, on_device=False):
 class Threshold:
     """A pick threshold formed on the device: scale x value[0] (value: a 1-element float32 CUDA tensor, e.g.
     correlogram_max(c, on_device=True)) -- the reference's `0.45 * np.max(corr_m)` (scripts/main_mfdetect.py:82,95) without the
-    host waiting for the maximum; the product is formed in float64 like the host's.  Accepted wherever pick_times /
+    host waiting for the maximum; the product is formed in float64 like the host's.  A NaN value (the maximum of a block
+    with a dead channel, detect._nan_dead_rows) or a NaN scale gives a NaN bar, and a NaN bar yields no pick in any row, as
+    scipy.signal.find_peaks(x, prominence=nan) does -- the same holds of a NaN passed as a plain number.  A +inf bar yields no
+    pick either, even in a row that holds +inf (SciPy keeps such a sample: DESIGN.md).  Accepted wherever pick_times /
     pick_times_env take a threshold."""
 
     def __init__(self, scale, value):
