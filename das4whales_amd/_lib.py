@@ -120,7 +120,16 @@ def _load():
         "d4w_nmf_normalise_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                           ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
-        "d4w_semblance_limits": (c_int, [P(c_int), P(c_int), P(c_int), P(c_int)]),
+        "d4w_stalta_max_window": (c_int, []),
+        "d4w_stalta_tile": (c_int, []),
+        "d4w_stalta_f32": (c_int, [c_void_p, ctypes.c_size_t, c_int, c_int, c_void_p, ctypes.c_size_t, c_int, c_int, c_int, c_int, c_int,
+                                   ctypes.c_double, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_size_t, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+        "d4w_trigger_onset_f32": (c_int, [c_void_p, ctypes.c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_int, c_void_p]),
+        "d4w_pack_events_i64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p,
+                                        c_void_p]),
+        "d4w_semblance_limits":(c_int, [P(c_int), P(c_int), P(c_int), P(c_int)]),
         "d4w_semblance_tile": (c_int, [P(c_int), P(c_int)]),
         "d4w_semblance_f32": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),

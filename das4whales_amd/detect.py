@@ -890,6 +890,282 @@ def pick_times(corr_m, threshold, lazy=False):
 
 
 # ---------------------------------------------------------------------------------------------
+# STA/LTA energy detector and trigger events (no reference counterpart; DESIGN.md 3.3c, csrc/stalta.hip)
+# ---------------------------------------------------------------------------------------------
+_STALTA_FORMS = {"classic": 0, "recursive": 1}
+
+
+class StaLtaState:
+    """What sta_lta / trigger_onset / sta_lta_events of block k hand to block k + 1 (opaque): the last max(nsta, nlta + gap) - 1
+    samples of every row (classic form; fewer while the record is shorter), the float64 (sta, lta) of every row and the number
+    of samples seen (recursive form), the trigger's active flag of every row (None before a trigger has run)."""
+
+    __slots__ = ("key", "tail", "rec", "seen", "active")
+
+    def __init__(self, key, tail=None, rec=None, seen=0, active=None):
+        self.key, self.tail, self.rec, self.seen, self.active = key, tail, rec, int(seen), active
+
+    def with_active(self, active):
+        return StaLtaState(self.key, self.tail, self.rec, self.seen, active)
+
+
+def _stalta_check(data, nsta, nlta, gap, form, floor):
+    if getattr(data, "ndim", 0) != 2:
+        raise ValueError("x must be a 2-D [channel x time] array")
+    if form not in _STALTA_FORMS:
+        raise ValueError("form must be 'classic' or 'recursive', not %r" % (form,))
+    for name, v in (("nsta", nsta), ("nlta", nlta), ("gap", gap)):
+        if int(v) != v:
+            raise ValueError("%s must be a whole number of samples" % name)
+    nsta, nlta, gap = int(nsta), int(nlta), int(gap)
+    wmax = int(lib.d4w_stalta_max_window())
+    if nsta < 1 or nlta < 1 or gap < 0:
+        raise ValueError("nsta and nlta must be at least 1 and gap at least 0")
+    if form == "recursive" and gap != 0:
+        raise ValueError("the recursive form takes gap = 0")
+    if nlta + gap > wmax or nsta > wmax:
+        raise ValueError("nlta + gap (and nsta) must not exceed %d samples" % wmax)
+    if not (np.isfinite(floor) and floor >= 0):
+        raise ValueError("floor must be finite and >= 0")
+    return nsta, nlta, gap
+
+
+def _rows_in_place(x):
+    """x as the kernels read it: a float32 CUDA tensor with unit time stride and a row pitch stays as it is."""
+    if dev.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 \
+            and (x.shape[0] == 1 or x.stride(0) >= x.shape[1]):
+        return x
+    return dev.to_device_f32(x)
+
+
+def _stalta_scale(xd, scale):
+    nx = xd.shape[0]
+    if scale is None:                                        # the row's max|x| in this block
+        xc = xd if xd.is_contiguous() else dsp._copy_cols(xd, torch.empty(tuple(xd.shape), dtype=torch.float32, device=xd.device))
+        return _row_stats_cached(xc)[1]
+    s = scale.to(device=xd.device, dtype=torch.float32).contiguous() if dev.is_tensor(scale) \
+        else torch.from_numpy(np.ascontiguousarray(scale, dtype=np.float32)).to(xd.device)
+    if s.dim() != 1 or s.numel() != nx:
+        raise ValueError("scale needs one value for each of the %d channels" % nx)
+    return s
+
+
+def _event_bars(thr, nx, device):
+    """A trigger threshold (a number, a Threshold, a ChannelThreshold, nx values) as nx float64 values on the device."""
+    rows = _per_channel(thr, nx)
+    if rows is None:
+        return torch.full((nx,), float(thr), dtype=torch.float64, device=device)
+    if isinstance(rows, ChannelThreshold):
+        if rows.values.device != device:
+            raise ValueError("the threshold's values live on another device than the block")
+        return rows.values.to(torch.float64) * rows.scale      # the product in float64, as the pickers form it
+    return torch.from_numpy(np.ascontiguousarray(thr, dtype=np.float64).reshape(-1)).to(device)
+
+
+def _event_thresholds(thr_on, thr_off, nx, device):
+    on, off = _event_bars(thr_on, nx, device), _event_bars(thr_off, nx, device)
+    if bool((off > on).any()):
+        raise ValueError("thr_off must not exceed thr_on on any channel")
+    return on, off
+
+
+class EventRows(collections.abc.Sequence):
+    """The trigger events of every channel: a read-only Sequence of per-channel [n, 3] int64 arrays (on, off, peak_index), backed
+    by one packed 4 x K table on the device (`packed`: channel, on, off, peak_index) and the K peak values (`packed_peak`);
+    nothing is copied to the host until a row, .table() or .peak is asked for.  on = -1: the event was active on entry;
+    off = ns: it is still open at the end of the block."""
+
+    def __init__(self, packed, packed_peak, counts):
+        self.packed, self.packed_peak, self.counts = packed, packed_peak, counts
+        self._host = None
+
+    def _rows(self):
+        if self._host is None:
+            cnt = self.counts.cpu().numpy().astype(np.int64)
+            self._host = (np.ascontiguousarray(self.packed[1:].cpu().numpy().T), np.concatenate(([0], np.cumsum(cnt))))
+        return self._host
+
+    def __len__(self):
+        return int(self.counts.shape[0])
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        flat, off = self._rows()
+        i = int(i)
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError("channel index out of range")
+        return flat[off[i]:off[i + 1]]
+
+    @property
+    def total(self):
+        return int(self.packed.shape[1])
+
+    def table(self):
+        """4 x K int64 ndarray: channel, on, off, peak_index."""
+        return self.packed.cpu().numpy()
+
+    @property
+    def peak(self):
+        """The K float32 peak values, in the table's order."""
+        return self.packed_peak.cpu().numpy()
+
+    def picks(self, which="on"):
+        """The events as picks -- a PickRows, taken by everything that takes pick_times' result (convert_pick_times,
+        select_picked_times, loc.associate_picks, shard.all_gather_picks): which="on" the onsets (an event that was already
+        active on entry, on = -1, contributes none), which="peak" the peak positions."""
+        if which == "peak":
+            return PickRows(self.packed[[0, 3]].contiguous(), self.counts)
+        if which != "on":
+            raise ValueError("which must be 'on' or 'peak'")
+        keep = self.packed[1] >= 0
+        cnt = self.counts.to(torch.int64) - torch.bincount(self.packed[0][~keep], minlength=len(self))
+        return PickRows(self.packed[:2][:, keep].contiguous(), cnt.to(torch.int32))
+
+
+def _stalta_device(xd, nsta, nlta, gap, form, floor, scale, state, want_ratio, bars=None, cap0=1024):
+    """One pass of csrc/stalta.hip over xd (float32 CUDA [nx, ns], any row pitch) -> (ratio or None, EventRows or None, the
+    state after the block).  bars: (thr_on, thr_off) float64 device tensors -- the trigger runs on the ratios in registers."""
+    nx, ns = xd.shape
+    device = xd.device
+    key = (form, nsta, nlta, gap)
+    if isinstance(state, StaLtaState) and state.key is None:         # a flag from trigger_onset alone
+        state = StaLtaState(key, active=state.active)
+    if state is not None and (not isinstance(state, StaLtaState) or state.key != key):
+        raise ValueError("state comes from a call with other parameters (form, nsta, nlta, gap)")
+    classic = form == "classic"
+    A = _stalta_scale(xd, scale)
+    need = max(nsta, nlta + gap) - 1
+    tail = state.tail if state is not None and classic else None
+    if tail is not None and (tail.shape[0] != nx or tail.device != device):
+        raise ValueError("state belongs to a block of another shape or device")
+    rin = state.rec if state is not None and not classic else None
+    seen = state.seen if state is not None else 0
+    rout = torch.empty((nx, 2), dtype=torch.float64, device=device) if not classic else None
+    ratio = torch.empty((nx, ns), dtype=torch.float32, device=device) if want_ratio else None
+    act_in = state.active if state is not None and bars is not None else None
+    stream = torch.cuda.current_stream(device)
+    events = act_out = None
+
+    def launch(cap):
+        ev = pk = cnt = None
+        if bars is not None:
+            ev = torch.empty((nx, cap, 3), dtype=torch.int32, device=device)
+            pk = torch.empty((nx, cap), dtype=torch.float32, device=device)
+            cnt = torch.empty(nx, dtype=torch.int32, device=device)
+        o = lambda t: dev.ptr(t) if t is not None else None
+        check(lib.d4w_stalta_f32(dev.ptr(xd), int(xd.stride(0)) if nx > 1 else ns, nx, ns, o(tail), int(tail.stride(0)) if tail is not None else 0,
+                                 int(tail.shape[1]) if tail is not None else 0, _STALTA_FORMS[form], nsta, nlta, gap, float(floor),
+                                 dev.ptr(A), o(rin), o(rout), seen, o(ratio), ns if ratio is not None else 0,
+                                 o(bars[0]) if bars else None, o(bars[1]) if bars else None, o(act_in), o(act_out), o(ev), o(pk), o(cnt),
+                                 cap, int(stream.cuda_stream)))
+        return ev, pk, cnt
+
+    with torch.cuda.device(device):
+        if bars is not None:
+            act_out = torch.empty(nx, dtype=torch.int32, device=device)
+            events = _pack_events(launch, nx, ns, cap0, device, stream)
+        else:
+            launch(0)
+        # the tail is COPIED out (one strided-copy launch): a view would keep the whole block alive for one more call
+        new_tail = None
+        if classic and need > 0:
+            if ns >= need:
+                new_tail = dsp._copy_cols(xd[:, ns - need:], torch.empty((nx, need), dtype=torch.float32, device=device))
+            else:
+                keep = min(need - ns, tail.shape[1]) if tail is not None else 0
+                new_tail = dsp._concat_cols(([tail[:, tail.shape[1] - keep:]] if keep else []) + [xd])
+    return ratio, events, StaLtaState(key, new_tail, rout, seen + ns, act_out)
+
+
+def _pack_events(launch, nx, ns, cap0, device, stream):
+    """Run launch(cap) -> (ev, peak, counts) until every row's events fit, then pack the rows: one host synchronisation."""
+    cap = max(1, min(ns // 2 + 1, int(cap0)))
+    off = torch.empty(nx, dtype=torch.int64, device=device)
+    summ = torch.empty(2, dtype=torch.int64, device=device)
+    while True:
+        ev, pk, cnt = launch(cap)
+        check(lib.d4w_pick_offsets_i64(dev.ptr(cnt), nx, dev.ptr(off), dev.ptr(summ), int(stream.cuda_stream)))
+        with torch.cuda.stream(stream):
+            need, total = (int(v) for v in summ.cpu())
+        if need <= cap:
+            break
+        cap = min(ns // 2 + 1, max(need, 2 * cap))
+    packed = torch.empty((4, total), dtype=torch.int64, device=device)
+    peaks = torch.empty(total, dtype=torch.float32, device=device)
+    check(lib.d4w_pack_events_i64(dev.ptr(ev), dev.ptr(pk), dev.ptr(cnt), dev.ptr(off), nx, cap, total,
+                                  dev.ptr(packed) if total else None, dev.ptr(peaks) if total else None, int(stream.cuda_stream)))
+    return EventRows(packed, peaks, cnt)
+
+
+def sta_lta(x, nsta, nlta, *, gap=0, form="classic", floor=1e-6, scale=None, state=None, return_state=False):
+    """STA/LTA ratio of the energy e = x^2 of every row of a [channel x time] block, in the caller's container (a float32 CUDA
+    tensor with unit time stride and a row pitch is read in place):
+        form="classic"    STA[i] = mean e[i-nsta+1 .. i],  LTA[i] = mean e[i-gap-nlta+1 .. i-gap]  (the gap keeps a call out of
+                          its own noise estimate);  r = STA / LTA where both windows lie in known samples and LTA > (floor A)^2
+        form="recursive"  sta[i] = sta[i-1] + (e[i] - sta[i-1]) / nsta, lta likewise with nlta (gap = 0), both from 0 or from
+                          `state`;  r = sta / lta once nlta samples have been seen and lta > (floor A)^2
+    and 0 elsewhere.  A = scale[c] when `scale` holds one value per channel (a noise level, or a fixed level for a stream of
+    files), else the row's max|x| in this block: results do not depend on the row's gain; dropouts and dead channels give 0.
+    state: the StaLtaState an earlier call returned with return_state=True -- the block then continues that record, and the
+    result equals the one call on the concatenation.  nlta + gap (and nsta) <= d4w_stalta_max_window() = 16384.  Inputs are
+    finite: a NaN or Inf sample gives unspecified ratios downstream of it."""
+    nsta, nlta, gap = _stalta_check(x, nsta, nlta, gap, form, floor)
+    ratio, _, new = _stalta_device(_rows_in_place(x), nsta, nlta, gap, form, floor, scale, state, True)
+    if state is not None:
+        new = new.with_active(state.active)
+    out = dev.like_input(ratio, x)
+    return (out, new) if return_state else out
+
+
+def trigger_onset(r, thr_on, thr_off, *, state=None, return_state=False, _cap0=1024):
+    """Events of every row of the ratio r ([channel x time]): a sample is ON if r > thr_on[c], OFF if r < thr_off[c], KEEP
+    otherwise (a NaN keeps); the flag after a sample is the last ON / OFF at or before it, else the flag `state` carries in.
+    An event is a maximal run of active samples -> EventRows of (on, off, peak_index) per channel, `.peak` the largest r of
+    every run.  thr_on / thr_off: numbers or one value per channel, in the forms pick_times takes (ChannelThreshold included);
+    thr_off <= thr_on per channel.  return_state=True: also the state with the flag after the last sample."""
+    if getattr(r, "ndim", 0) != 2:
+        raise ValueError("r must be a 2-D [channel x time] array")
+    rd = _rows_in_place(r)
+    nx, ns = rd.shape
+    if state is not None and not isinstance(state, StaLtaState):
+        raise ValueError("state must be a StaLtaState")
+    on, off = _event_thresholds(thr_on, thr_off, nx, rd.device)
+    act_in = state.active if state is not None else None
+    stream = torch.cuda.current_stream(rd.device)
+    with torch.cuda.device(rd.device):
+        act_out = torch.empty(nx, dtype=torch.int32, device=rd.device)
+
+        def launch(cap):
+            ev = torch.empty((nx, cap, 3), dtype=torch.int32, device=rd.device)
+            pk = torch.empty((nx, cap), dtype=torch.float32, device=rd.device)
+            cnt = torch.empty(nx, dtype=torch.int32, device=rd.device)
+            check(lib.d4w_trigger_onset_f32(dev.ptr(rd), int(rd.stride(0)) if nx > 1 else ns, nx, ns, dev.ptr(on), dev.ptr(off),
+                                            dev.ptr(act_in) if act_in is not None else None, dev.ptr(act_out), dev.ptr(ev), dev.ptr(pk),
+                                            dev.ptr(cnt), cap, int(stream.cuda_stream)))
+            return ev, pk, cnt
+        events = _pack_events(launch, nx, ns, _cap0, rd.device, stream)
+    if not return_state:
+        return events
+    new = state.with_active(act_out) if state is not None else StaLtaState(None, active=act_out)
+    return events, new
+
+
+def sta_lta_events(x, nsta, nlta, thr_on, thr_off, *, gap=0, form="classic", floor=1e-6, scale=None, state=None, return_state=False,
+                   _cap0=1024):
+    """trigger_onset(sta_lta(x, ...), thr_on, thr_off) in ONE read of x and no ratio written (4 B per sample instead of 8 + 4):
+    the ratios are formed by the same device function and handed to the trigger in registers -- the events equal the
+    composition's exactly.  Arguments as sta_lta and trigger_onset; the state carries the samples and the flag."""
+    nsta, nlta, gap = _stalta_check(x, nsta, nlta, gap, form, floor)
+    xd = _rows_in_place(x)
+    bars = _event_thresholds(thr_on, thr_off, xd.shape[0], xd.device)
+    _, events, new = _stalta_device(xd, nsta, nlta, gap, form, floor, scale, state, False, bars=bars, cap0=_cap0)
+    return (events, new) if return_state else events
+
+
+# ---------------------------------------------------------------------------------------------
 # spectrogram correlation
 # ---------------------------------------------------------------------------------------------
 def _keep_bins(fs, nperseg, fmin, fmax):

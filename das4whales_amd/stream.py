@@ -29,7 +29,8 @@ from . import detect, dsp
 
 
 class FileStream:
-    def __init__(self, fs, fmin, fmax, templates=(), fk_mask=None, halo=1024, prev_tail=None, on_filtered=None, nmf=None):
+    def __init__(self, fs, fmin, fmax, templates=(), fk_mask=None, halo=1024, prev_tail=None, on_filtered=None, nmf=None,
+                 sta_lta=None):
         """fs, fmin, fmax: band-pass (dsp.bp_filt arguments); templates: full-length or support-only
         template vectors (detect.gen_template_fincall output) for the matched filter; fk_mask: f-k mask
         for one file's shape (any form dsp.fk_filter_filt accepts) or None to skip the f-k filter.
@@ -38,7 +39,12 @@ class FileStream:
         file's band-passed (+ f-k filtered) version exists (the neighbour that needs its head can be served early).
         nmf: None (default: the peak-normalised matched filter, results carry "correlograms") or True / a dict with `center`
         and / or `floor` (detect.compute_nmf_correlograms' arguments): the window-normalised matched filter instead -- results
-        carry "nmf" and its "row_max" in place of "correlograms", the last lags completed from the next file's head alike."""
+        carry "nmf" and its "row_max" in place of "correlograms", the last lags completed from the next file's head alike.
+        sta_lta: None (default) or a dict that turns the STA/LTA energy detector on (detect.sta_lta_events): `nsta`, `nlta`,
+        `thr_on`, `thr_off` (required), `gap`, `form`, `floor`, `scale`, `keep_ratio` (optional).  Every filtered file's events
+        are computed with the detect.StaLtaState the file before left -- the windows and the trigger's flag run across the seams
+        -- and the results carry "events" (a detect.EventRows; an event across a seam arrives as (on, ns) and (-1, off)) and,
+        with keep_ratio=True, "sta_lta".  templates=() stays legal: the energy detector alone."""
         self.fs, self.fmin, self.fmax = float(fs), float(fmin), float(fmax)
         self.halo = int(halo)
         self.taps = [detect._normalised_support(t) for t in templates]
@@ -54,8 +60,17 @@ class FileStream:
             parts = [detect._nmf_parts(t) for t in templates]
             # the numerator's taps are the supports de-meaned over themselves, without the zero-padded templates' DC tail
             self.taps, self.tail, self._norms = [h for h, _ in parts], [0.0] * len(parts), [n for _, n in parts]
+        self.sta_lta = None
+        if sta_lta is not None:
+            opts = dict(sta_lta)
+            need, may = {"nsta", "nlta", "thr_on", "thr_off"}, {"gap", "form", "floor", "scale", "keep_ratio"}
+            if (need - set(opts)) or (set(opts) - need - may):
+                raise ValueError("sta_lta takes a dict with %s and optionally %s, not %r" % (sorted(need), sorted(may), sorted(opts)))
+            self._sl_keep = bool(opts.pop("keep_ratio", False))
+            self._sl_bars = (opts.pop("thr_on"), opts.pop("thr_off"))
+            self.sta_lta, self._sl_state = opts, None
         self.fk_mask = fk_mask
-        self._raw = []          # raw files waiting for their right halo: [(index, tensor)]
+        self._raw = []        # raw files waiting for their right halo: [(index, tensor)]
         self._prev_tail = dev.to_device_f32(prev_tail) if prev_tail is not None else None   # last `halo` raw samples of the file before self._raw[0]
         self._on_filtered = on_filtered
         self._filt = []         # filtered (band-pass [+ f-k]) files waiting for the next file's head
@@ -122,6 +137,16 @@ class FileStream:
                                                                want_row_max=True)
             if rmax is not None:
                 out["row_max"] = rmax        # max over the lags of every row, per template (detect.correlogram_max)
+        if self.sta_lta is not None:
+            # files reach this point in order: the state (the samples the windows reach back to, copied out of the file
+            # before; the recurrences' values; the trigger's flag) is the one the previous filtered file left
+            if self._sl_keep:
+                out["sta_lta"], st = detect.sta_lta(y, state=self._sl_state, return_state=True, **self.sta_lta)
+                out["events"], self._sl_state = detect.trigger_onset(out["sta_lta"], *self._sl_bars, state=st, return_state=True)
+            else:
+                out["events"], self._sl_state = detect.sta_lta_events(y, self.sta_lta["nsta"], self.sta_lta["nlta"], *self._sl_bars,
+                                                                      state=self._sl_state, return_state=True,
+                                                                      **{k: v for k, v in self.sta_lta.items() if k not in ("nsta", "nlta")})
         return out
 
     # ------------------------------------------------------------------------------------------

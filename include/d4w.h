@@ -402,6 +402,55 @@ int d4w_nmf_normalise_f32(const float* x, int nx, int ns, const float* xnext, in
                           double norm0, double norm1, int center, double floor, float* y0, float* y1,
                           float* rowmax0, float* rowmax1, void* stream);
 
+/* STA/LTA energy detector and its on/off trigger (das4whales_amd/csrc/stalta.hip; no reference counterpart):
+ * the template-free detector per channel.  With e[i] = x[c][i]^2 (the float32 sample widened to float64), samples before the
+ * block at negative i:
+ *   form 0, classic     STA[i] = (1/nsta) sum e[i-nsta+1 .. i],   LTA[i] = (1/nlta) sum e[i-gap-nlta+1 .. i-gap]
+ *                       r[i] = STA / LTA  where both windows lie in known samples and LTA > (floor A)^2,  0 elsewhere
+ *   form 1, recursive   sta[i] = sta[i-1] + (e[i] - sta[i-1]) / nsta, lta likewise with nlta (gap = 0), from rstate_in or 0
+ *                       r[i] = sta / lta  where nseen + i + 1 >= nlta and lta > (floor A)^2,  0 elsewhere
+ * A = scale[c] (DEVICE [nx]: the row's max|x| from d4w_row_stats_f32, or a per-channel noise level); a row with A = 0 (or NaN)
+ * gives zeros.  Known samples: the block's own and the n_prev before it, prev = DEVICE [nx][ld_prev] whose columns
+ * 0 .. n_prev - 1 are samples -n_prev .. -1 (classic form; the last max(nsta, nlta + gap) - 1 are all that is read).
+ * rstate_in / rstate_out = DEVICE [nx][2] float64 (sta, lta) before / after the block (recursive form; NULL: zeros / not
+ * wanted), nseen = samples of the record before the block.  x = DEVICE [nx][ld], ld in ELEMENTS (ld >= ns: a view is read in
+ * place); ratio = DEVICE [nx][ld_r] or NULL.
+ * Events (all of thr_on .. counts NULL: none): the trigger of d4w_trigger_onset_f32 runs on the ratios in registers; with
+ * ratio == NULL nothing but the events is written (4 B per sample instead of 8 + 4).  Same arithmetic as the two calls in turn.
+ * Numerics: every window sum is a float64 sum of parts of THAT window (samples, 8-sample runs, 64- and 512-sample blocks, all
+ * non-negative): its error is relative to what the window holds and a window of zeros sums to 0.  The recursive form is a
+ * float64 scan of (a, b) pairs.  One float64 division, rounded once to float32.  A NaN or Inf sample gives unspecified ratios
+ * downstream of it.  Bytes: x read once, r written once; a tile's halo is read again from L2 by the workgroup that walks the row.
+ * d4w_stalta_max_window() = 16384: the largest nlta + gap (and nsta); d4w_stalta_tile() = 2048: the samples of one anchor
+ * period (one workgroup's tile; what the tests size their row ends by).
+ * Errors: D4W_EINVAL for a NULL x or scale, nx or ns < 1, ld < ns, a form other than 0 / 1, nsta or nlta < 1, gap < 0, gap != 0
+ * in the recursive form, nlta + gap or nsta > d4w_stalta_max_window(), a floor that is negative or not finite, n_prev < 0 or
+ * > ld_prev or without prev, nseen < 0, neither ratio nor events asked for, ld_r < ns, some but not all of thr_on, thr_off, ev,
+ * peak, counts, cap < 1. */
+int d4w_stalta_max_window(void);
+int d4w_stalta_tile(void);
+int d4w_stalta_f32(const float* x, size_t ld, int nx, int ns, const float* prev, size_t ld_prev, int n_prev, int form,
+                   int nsta, int nlta, int gap, double floor, const float* scale, const double* rstate_in,
+                   double* rstate_out, long long nseen, float* ratio, size_t ld_r, const double* thr_on,
+                   const double* thr_off, const int32_t* active_in, int32_t* active_out, int32_t* ev, float* peak,
+                   int32_t* counts, int cap, void* stream);
+/* Trigger events of the rows of r = DEVICE [nx][ld]: sample i is ON if r[i] > thr_on[c], OFF if r[i] < thr_off[c], KEEP
+ * otherwise (a NaN is KEEP); the flag after sample i is the last ON / OFF at or before it, else active_in[c] (DEVICE int32 [nx],
+ * NULL: inactive).  thr_on, thr_off = DEVICE [nx] float64, thr_off <= thr_on (not checked: they are on the device).  An event is
+ * a maximal run of active samples: on = its first sample (-1: active on entry), off = one past its last (ns: still open),
+ * peak index / peak = the position and value of the largest r of the run inside this block (the first on ties; -inf at the run's
+ * first sample when it holds NaNs only).  Per row the first min(count, cap) events go to ev[c][cap][3] = (on, off, peak index)
+ * and peak[c][cap], the true count to counts[c] (cap = ns / 2 + 1 always suffices; the caller repeats with a larger cap), the
+ * flag after the last sample to active_out[c] (or NULL).  d4w_pick_offsets_i64(counts) and d4w_pack_events_i64 pack the rows into
+ * out[4][total] int64 = (channel, on, off, peak index) and peak_out[total].
+ * Errors: D4W_EINVAL for a NULL r / thr_on / thr_off / ev / peak / counts, nx or ns < 1, ld < ns, cap < 1 (pack: total < 0,
+ * NULL out with total > 0). */
+int d4w_trigger_onset_f32(const float* r, size_t ld, int nx, int ns, const double* thr_on, const double* thr_off,
+                          const int32_t* active_in, int32_t* active_out, int32_t* ev, float* peak, int32_t* counts,
+                          int cap, void* stream);
+int d4w_pack_events_i64(const int32_t* ev, const float* peak, const int32_t* counts, const int64_t* offsets, int nx, int cap,
+                        int64_t total, int64_t* out, float* peak_out, void* stream);
+
 /* Local slant-stack semblance (das4whales_amd/csrc/semblance.hip; no reference counterpart): per channel and
  * sample the coherence of the 2M + 1 neighbouring channels along np trial moveouts, and the trial that maximises it.
  *   x = DEVICE [nx][pitch] float32, pitch in ELEMENTS (pitch >= ns: a column-sliced view is read in place).
