@@ -254,6 +254,12 @@ def _load():
         "d4w_project_subtract_f32": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p,
                                              c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p,
                                              ctypes.c_int64, c_void_p]),
+        "d4w_coherence_limits": (c_int, [P(c_int), P(c_int), P(c_int), P(c_int)]),
+        "d4w_coherence_ws_bytes": (c_int, [c_int, c_int, c_int, c_int, P(ctypes.c_size_t)]),
+        "d4w_coherence_f32": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, ctypes.c_int64, c_int, c_void_p, ctypes.c_int64,
+                                      c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "d4w_coherence_peak_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch: fail loudly

@@ -49,7 +49,7 @@ namespace d4w {
 constexpr int kBeamThreads = 256;
 constexpr int kBeamCpt = 4;                                   // columns per thread
 constexpr int kBeamTile = kBeamThreads * kBeamCpt;            // columns per workgroup
-constexpr int kBeamSegment = 128;                             // channels one thread sums from 0
+// kBeamSegment, the channels one thread sums from 0: taps.h (coherence.hip sums in the same segments)
 constexpr int kBeamMaxCalls = 65535;                          // grid limit
 constexpr int kBeamMaxLength = kMoveoutDelayMax;              // a beam is no longer than the longest delay
 

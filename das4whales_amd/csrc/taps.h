@@ -29,6 +29,10 @@ __device__ __forceinline__ void delay_taps(float w, float f, float (&l)[ORDER + 
     }
 }
 
+// the channels one thread of the beam sums from 0 (beam.hip says why 128): the beam and the sums of coherence.hip split the
+// channels in the same fixed segments, so that the latter's b plane is the beam bit for bit
+constexpr int kBeamSegment = 128;
+
 // a window of len samples: sample i is pa[i] for i < split, pb[i - split] after; len = 0: not valid, never read
 struct LevelWindow {
     const float* pa;

@@ -14,7 +14,9 @@ window that follows the moveout, the mean square of a noise window before it, th
 and an SNR in dB and `fit_spreading` fits the level against range; `project_calls`, `subtract_calls` and `remove_calls`
 (csrc/project.hip) are the transpose of the beam: the call's waveform laid back on every channel along its moveout, fitted
 (a signed least-squares amplitude and a correlation coefficient per channel) and subtracted, so that a second pass over the
-residual sees the weaker call underneath.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
+residual sees the weaker call underneath; `beam_coherence` and `beamform_pws` (csrc/coherence.hip) say whether anything coherent
+arrived from a position at all -- the windowed semblance of the beam and the phase coherence of the analytic signal along the
+moveout, both in [0, 1] whatever the loudness -- and give the phase-weighted stack.  NumPy in -> NumPy float64 out; a CUDA tensor in -> a float64 tensor on the
 same device and stream.  The four small per-channel helpers (distances, radii, angles) are host float64 arithmetic for NumPy input, like the
 index arithmetic of the other namespaces; for tensors they stay on the device.
 
@@ -24,6 +26,7 @@ notion -- its np.min(Ti) turns the whole result into NaN).
 import ctypes
 import math
 import sys
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -59,7 +62,7 @@ def _f64(x, device=None):
 # (relocate returns what its last solve_robust_batch does).  _out serves the later families: any tensor in, on the host or on a
 # device, gives a tensor on the device the work ran on, and only NumPy in gives NumPy back.  It is the rule of vote_grid,
 # associate_picks, delay_table, stack_grid, stack_best, arrivals_near, locate_stack, beam_delays, beamform, refine_arrivals,
-# received_levels, project_calls, subtract_calls and remove_calls.  The small arithmetic (the four per-channel helpers,
+# received_levels, project_calls, subtract_calls, remove_calls, beam_coherence and beamform_pws.  The small arithmetic (the four per-channel helpers,
 # levels_db, fit_spreading) stays in the container it was given.
 def _back(y, *templates):
     """The device result in the callers' container: a tensor where any input was one (on the host if none was on a device)."""
@@ -1465,3 +1468,145 @@ def remove_calls(trace, fs, cable_pos, c0, pos, start, length, order=1, min_coef
         return res
     parts = tuple(_out(t, a.as_tensor) for t in (beam, amp, coef))
     return (res,) + parts if next_block is None else res + parts
+
+
+# ------------------------------------------------------------------------------------------
+# beyond the reference: coherence of located calls along their moveout -- semblance, phase-weighted stack (csrc/coherence.hip)
+# ------------------------------------------------------------------------------------------
+Coherence = namedtuple("Coherence", ["beam", "semblance", "phase", "wsum", "times", "peak", "peak_index"])
+
+
+def coherence_limits():
+    """(largest number of calls, largest length, largest half_window, channels per summation segment) of the coherence kernels."""
+    a, b, h, s = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib.d4w_coherence_limits(ctypes.byref(a), ctypes.byref(b), ctypes.byref(h), ctypes.byref(s)))
+    return a.value, b.value, h.value, s.value
+
+
+def _coherence_check(a, trace, next_block, weights, length, half_window, imag, next_imag, peak_range, max_half):
+    """The arguments only beam_coherence has, on the host before any device work: (nt, H, (lo, hi))."""
+    nt = _whole(a.ns if length is None else length, "length", 1, a.max_length)
+    H = _whole(half_window, "half_window", 0, max_half)
+    if weights is not None and not (dev.is_tensor(weights) and weights.is_cuda):
+        w = np.asarray(weights.numpy() if dev.is_tensor(weights) else weights, dtype=np.float64)
+        if not (np.all(np.isfinite(w)) and np.all(w >= 0)):
+            raise ValueError("weights must be finite and >= 0")
+    if imag is None or imag is False:
+        if next_imag is not None:
+            raise ValueError("next_imag without imag")
+    elif imag is True:
+        if next_imag is not None:
+            raise ValueError("imag=True forms the imaginary part of next_block here: next_imag must be None")
+    else:
+        for what, b, like, other in (("imag", imag, trace, "trace"), ("next_imag", next_imag, next_block, "next_block")):
+            if (b is None) != (like is None):
+                raise ValueError("next_imag is given if and only if next_block is")
+            if b is not None and (getattr(b, "ndim", 0) != 2 or _shape(b) != _shape(like)):
+                raise ValueError("%s must have the shape %s of %s, got %s" % (what, _shape(like), other, _shape(b)))
+    lo, hi = (0, nt) if peak_range is None else (peak_range if _shape(peak_range) == (2,) else (None, None))
+    if lo is None:
+        raise ValueError("peak_range must be None or (lo, hi), got %r" % (peak_range,))
+    lo = _whole(lo, "peak_range[0]", 0, nt - 1)
+    return nt, H, (lo, _whole(hi, "peak_range[1]", lo + 1, nt))
+
+
+def _coherence(a, nt, order, H, im, pitch_im, imn, pitch_imn, rng):
+    """The kernels on device tensors: (beam, semblance, phase or None, wsum) float32 [ncalls x nt], peak float32 and peak_index
+    int32 [ncalls]; no launch without a call."""
+    d = a.device
+    beam, semb, wsum = (torch.empty((a.ncalls, nt), dtype=torch.float32, device=d) for _ in range(3))
+    phase = torch.empty((a.ncalls, nt), dtype=torch.float32, device=d) if im is not None else None
+    peak = torch.empty((a.ncalls,), dtype=torch.float32, device=d)
+    index = torch.empty((a.ncalls,), dtype=torch.int32, device=d)
+    if a.ncalls:
+        nbytes = ctypes.c_size_t()
+        _lib.check(_lib.lib.d4w_coherence_ws_bytes(a.nch, a.ncalls, nt, int(im is not None), ctypes.byref(nbytes)))
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=d)
+        _lib.check(_lib.lib.d4w_coherence_f32(*_record(a), _p(im), pitch_im, _p(imn), pitch_imn, dev.ptr(a.kr), _p(a.f), _p(a.w), dev.ptr(a.s),
+                                              a.ncalls, nt, order, H, dev.out_ptr(beam), dev.out_ptr(semb), _p(phase, True), dev.out_ptr(wsum),
+                                              dev.out_ptr(ws), dev.stream_ptr(a.e)))
+        _lib.check(_lib.lib.d4w_coherence_peak_f32(dev.ptr(semb), a.ncalls, nt, rng[0], rng[1], dev.out_ptr(peak), dev.out_ptr(index),
+                                                   dev.stream_ptr(a.e)))
+    return beam, semb, phase, wsum, peak, index
+
+
+def beam_coherence(trace, fs, cable_pos, c0, pos, start=0, length=None, half_window=0, order=1, weights=None, next_block=None, imag=None,
+                   next_imag=None, peak_range=None, *, delays=None):
+    """Whether anything coherent arrived from the positions a solver returned: the windowed semblance of the beam along each
+    call's moveout (Neidell-Taner) and, with the imaginary part of the analytic signal, the phase coherence across the channels.
+    Both are amplitude-free numbers in [0, 1]: one threshold holds for every cable, file and sea state.  With w = weights[ch],
+    v(ch, j) the sample beamform reads for (c, ch, j) at this order and h(ch, j) the same interpolation of imag, over the
+    channels that contribute (weight not 0, every tap inside the record), in increasing order:
+        b[c, j] = sum w v          e[c, j] = sum w v^2          W[c, j] = sum w
+        pr = sum w v / a           pi = sum w h / a             a = sqrt(v^2 + h^2); a term with a = 0 adds nothing to pr, pi
+        semblance[c, j] = sum_tau b^2 / sum_tau (W e),  tau over [j - half_window, j + half_window] clipped to [0, length); 0 where
+                          the denominator is 0
+        phase[c, j]     = sqrt(pr^2 + pi^2) / W; 0 where W is 0
+    Returns the named tuple Coherence(beam, semblance, phase, wsum, times, peak, peak_index): beam = b, bit for bit
+    beamform(normalize=False) of the same arguments; semblance, phase (None without imag) and wsum = W, all float32
+    [ncalls x length]; times float64 as beamform's; peak float32 [ncalls] = the largest semblance of each call over the columns
+    peak_range = (lo, hi), default the whole length, and peak_index int32 [ncalls] the first column that attains it.  The gate
+    after locate_stack, associate_picks or relocate is  keep = result.peak >= thr.
+
+    trace, pos, start, length, order, weights, next_block, delays: as for beamform; weights must be finite and >= 0.
+    half_window: H >= 0 samples, at most coherence_limits()[2]; the window should hold a period or more of the call.
+    imag: None (no phase), an array of trace's shape holding imag(hilbert(trace)) -- with next_block given, next_imag holds the
+    next block's in the same way --, or True: formed here with dsp.hilbert_imag, block by block.  A per-file Hilbert transform
+    is inexact for a few samples at the seam between trace and next_block; a caller who needs it exact passes blocks cut from
+    a transform of the joined record.  CUDA float32 views with unit column stride are read in place with their row pitch.
+    float32 sums in increasing channel order in fixed segments of coherence_limits()[3] channels, window sums in increasing tau:
+    run-to-run bit-identical, independent of the other calls of the batch, and semblance keeps its bits under a power-of-two
+    scaling of trace.  Non-finite samples under a non-zero weight leave the elements they touch unspecified.  A bad argument
+    raises ValueError on the host before any device work (negative or non-finite weights in a CUDA tensor: before any launch).
+    NumPy in -> NumPy out; a CUDA tensor in -> tensors on that device and stream."""
+    a, ys = _coherence_run(trace, fs, cable_pos, c0, pos, start, length, half_window, order, weights, next_block, imag, next_imag, peak_range,
+                           delays)
+    return Coherence(*(None if y is None else _out(y, a.as_tensor) for y in ys))
+
+
+def _coherence_run(trace, fs, cable_pos, c0, pos, start, length, half_window, order, weights, next_block, imag, next_imag, peak_range, delays):
+    """beam_coherence on device tensors: (the checked arguments, (beam, semblance, phase or None, wsum, times, peak, peak_index))."""
+    order, kind = _order(order)
+    limits = coherence_limits()
+    a = _check(cable_pos, c0, fs, pos=pos, block=trace, name="trace", next_block=next_block, weights=weights, start=start,
+               table=(delays, kind), limits=limits[:2])
+    nt, H, rng = _coherence_check(a, trace, next_block, weights, length, half_window, imag, next_imag, peak_range, limits[2])
+    given = imag is not None and imag is not True and imag is not False
+    d = _upload(a, like=(imag, next_imag) if given else ()).device
+    with torch.cuda.device(d):
+        im, pitch_im, imn, pitch_imn = None, 0, None, 0
+        if given:
+            im, pitch_im = _env_block(imag, d)
+            if next_imag is not None:
+                imn, pitch_imn = _env_block(next_imag, d)
+        elif imag is True:
+            from . import dsp
+            im, pitch_im = _env_block(dsp.hilbert_imag(a.e), d)
+            if a.nb is not None:
+                imn, pitch_imn = _env_block(dsp.hilbert_imag(a.nb), d)
+        beam, semb, phase, wsum, peak, index = _coherence(a, nt, order, H, im, pitch_im, imn, pitch_imn, rng)
+        times = (a.s.to(torch.float64)[:, None] + torch.arange(nt, dtype=torch.float64, device=d)[None, :]) \
+            / torch.full((), a.fs, dtype=torch.float64, device=d)
+    return a, (beam, semb, phase, wsum, times, peak, index)
+
+
+def beamform_pws(trace, fs, cable_pos, c0, pos, start=0, length=None, power=2.0, order=1, weights=None, next_block=None, imag=True,
+                 next_imag=None, *, delays=None):
+    """Phase-weighted stack toward located calls: the normalized beam times the phase coherence of beam_coherence to the power
+    `power`,  (beam / wsum) * phase ** power  (0 where wsum is 0).  Stretches of the beam on which the channels do not agree in
+    phase are suppressed and coherent signals keep their waveform: signal-to-noise beyond the sqrt(channels) of a linear sum.
+    Returns (pws [ncalls x length] float32, times [ncalls x length] float64).  power >= 0; with power = 0 it is
+    beamform(normalize=True).  imag: True (formed here with dsp.hilbert_imag, block by block) or the imaginary block(s), as
+    for beam_coherence, whose other arguments, rules and containers apply."""
+    power = _number(power, "power")
+    if power < 0:
+        raise ValueError("power must be >= 0, got %r" % (power,))
+    if imag is None or imag is False:
+        raise ValueError("beamform_pws needs the analytic signal: imag must be True or the imaginary block")
+    a, (beam, _, phase, wsum, times, _, _) = _coherence_run(trace, fs, cable_pos, c0, pos, start, length, 0, order, weights, next_block, imag,
+                                                            next_imag, None, delays)
+    with torch.cuda.device(a.device):
+        live = wsum != 0
+        out = torch.where(live, beam / torch.where(live, wsum, torch.ones_like(wsum)), torch.zeros_like(beam)) \
+            * phase ** torch.full((), power, dtype=torch.float32, device=a.device)
+    return _out(out, a.as_tensor), _out(times, a.as_tensor)

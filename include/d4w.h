@@ -1153,6 +1153,54 @@ int d4w_project_subtract_f32(const float* x, int64_t pitch, int nch, int ns, con
                              const int64_t* start, const float* amp, int ncalls, int order, float* y, int64_t pitch_y,
                              float* ynext /* or NULL iff xnext is */, int64_t pitch_ynext, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Coherence of located calls along their moveout: windowed semblance of the beam and phase coherence of the analytic signal
+ * (das4whales_amd/csrc/coherence.hip; the reference has none of this).  Every pointer is DEVICE memory unless
+ * it returns a limit.
+ *
+ *   x, pitch, nch, ns, xnext, pitch_next, ns_next, k_or_r, f, weights, start, order: as for d4w_beamform_f32, with
+ *     weights[ch] >= 0 and finite.  ximag [nch][pitch_imag] or NULL: the imaginary part of the analytic signal of x (its
+ *     Hilbert transform), the same nch and ns; ximag_next [nch][pitch_imag_next]: that of xnext, given iff both are.
+ *   For call c, channel ch of weight w = weights[ch] and beam sample j, n = start[c] + j:
+ *     v(ch, j) = the record at n + delay[c][ch], interpolated exactly as d4w_beamform_f32 does for order 0, 1, 3;
+ *     h(ch, j) = the same interpolation of the imaginary block.
+ *     A term exists iff all of its taps lie inside the record [0, ns + ns_next); a channel of weight 0 is not read.
+ *   Over the contributing channels, in increasing order:
+ *     b[c][j] = sum w v          e[c][j] = sum w v^2          W[c][j] = sum w
+ *     pr = sum w v / a           pi = sum w h / a             a = sqrt(v^2 + h^2); a term with a = 0 adds nothing to pr, pi
+ *                                                             (its w stays in W)
+ *     semblance[c][j] = sum_tau b^2 / sum_tau (W e),  tau over [j - H, j + H] clipped to [0, length);  0 where the denominator is 0
+ *     phase[c][j]     = sqrt(pr^2 + pi^2) / W;  0 where W is 0
+ *   Both lie in [0, 1] (Cauchy-Schwarz per tau with w >= 0) up to float32 rounding.
+ *   float32 throughout: channel sums in increasing channel order in fixed segments of 128 channels, the segment partials
+ *   added in increasing order; window sums add their 2H + 1 terms in increasing tau; no running sums, no atomics: run-to-run
+ *   bit-identical and independent of the other calls of the batch.  The term w v is the beam's, so beam is bit for bit what
+ *   d4w_beamform_f32(normalize = 0) writes for the same arguments; e adds fmaf(t / w, t, e) with t = w v.  semblance keeps
+ *   its bits under a power-of-two scaling of x, absent underflow.  a = 0 means: the float32 v^2 + h^2 (of the weighted
+ *   terms) is below 2^-126.  Non-finite samples under a non-zero weight leave the elements they touch unspecified.
+ *
+ * d4w_coherence_limits: the largest ncalls (65535), length (2^30) and half window H (256), and the segment (128).
+ * d4w_coherence_ws_bytes: the bytes of workspace for that shape, phase = whether an imaginary block is given (never 0).
+ * d4w_coherence_f32: beam, semblance [ncalls][length]; phase [ncalls][length], given iff ximag is; wsum [ncalls][length]
+ *   (W) or NULL.  A NULL output is not written.
+ * d4w_coherence_peak_f32: per call the largest semblance over the columns [lo, hi) and the smallest column that attains it
+ *   (peak NaN and index -1 where the range holds nothing but NaN).
+ * Errors: D4W_EINVAL for a NULL required pointer (ws included), the shape and record errors of d4w_beamform_f32, an order
+ *   other than 0, 1, 3, order 1 or 3 without f, H outside 0 .. the limit, ximag without phase or the reverse, a pitch of an
+ *   imaginary block below its row, ximag_next without ximag, ximag_next given without xnext or missing with it, a weight that
+ *   is negative or not finite (the weights are copied to the host for this: the call waits for the stream when weights
+ *   are given), a peak range not inside [0, length).  Every error is reported before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int d4w_coherence_limits(int* max_calls, int* max_length, int* max_half_window, int* segment);
+int d4w_coherence_ws_bytes(int nch, int ncalls, int length, int phase, size_t* bytes);
+int d4w_coherence_f32(const float* x, int64_t pitch, int nch, int ns, const float* xnext /* or NULL */, int64_t pitch_next, int ns_next,
+                      const float* ximag /* or NULL */, int64_t pitch_imag, const float* ximag_next /* or NULL */,
+                      int64_t pitch_imag_next, const int32_t* k_or_r, const float* f /* NULL for order 0 */,
+                      const float* weights /* or NULL */, const int64_t* start, int ncalls, int length, int order, int half_window,
+                      float* beam, float* semblance, float* phase /* or NULL iff ximag is */, float* wsum /* or NULL */, void* ws,
+                      void* stream);
+int d4w_coherence_peak_f32(const float* semblance, int ncalls, int length, int lo, int hi, float* peak, int32_t* index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
